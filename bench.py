@@ -11,7 +11,11 @@ One "step" = one pass of the hot path over one batch: `dynamics()` on `--batch` 
 the state/tool update for every graph.  Multi-GPU: the batch shards across ranks with no data-path collective
 (weak scaling: per-GPU batch fixed), then ONE RCCL all-gather of the predicted states (north_star).
 
-Prints one JSON line on rank 0 (contract in the task statement) with
+A plain run sets up, warms up, times `--steps` passes and prints one JSON line on rank 0 (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed pass, `config`, and `ranks` for N > 1).
+`--dump-outputs DIR` writes what the last timed pass returned (`state_seqs`, `action_seqs`; float32) as DIR/<name>.npy, rows of a
+fixed seeded sample of the batch if the whole would exceed 64 MB; the inputs are seeded, so two builds can be compared output for output.
+`--full` adds everything below (each of `--no-profile`, `--no-extra`, `--no-cpu-baseline` drops its part of it):
   roofline      the edge encoder (MFMA-bound): achieved = F_min FLOP (140 100 per edge) x edges per
                 launch / average launch time, measured live with HIP events on the launch stream in a single-stream
                 pass, against the dense bf16/f16 MFMA peak (split modes) or the fp32 MFMA peak (f32 mode);
@@ -26,7 +30,7 @@ Prints one JSON line on rank 0 (contract in the task statement) with
   extra         (N = 1 only) the exact-fp32 engine mode on the same workload, BASELINE configs[2] / [3] per-GPU shapes
                 (granular-2k batch 128, cloth-4k batch 64 x 20 steps) and configs[4] (one MPPI iteration, 1024 x 15 on
                 rope-1k), each a short timed run of its own
-  ranks         (N > 1) per-rank rollout / all-gather milliseconds per step (min / max over ranks)
+  ranks         (N > 1) per-rank rollout / all-gather milliseconds per step (min / max over ranks; in a plain run too)
 """
 import argparse
 import contextlib
@@ -90,6 +94,40 @@ WORKLOADS = {"rope": dict(n_obj=1000, kw=dict(spacing=0.1)), "granular": dict(n_
              "cloth": dict(n_obj=4096, kw={})}
 PMC_FILE = os.path.join(ROOT, "profiles", "pmc_traffic.json")
 MEASURED_STREAM_GBS = 5800.0      # 7:1 read:write streaming ubench on an MI355X box (profiles/r03_hbm_bw_ubench.txt), for context next to the 8 TB/s spec peak
+DUMP_LIMIT_BYTES = 64 << 20       # --dump-outputs: at most this much in all
+
+
+def host_threads():
+    """CPU threads this process may use: its affinity mask, capped by OMP_NUM_THREADS when that is set (the oracle's OpenMP loop
+    runs that many).  os.cpu_count() counts the whole host, which on a shared box can be many times what a job is given."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    try:
+        omp = int(os.environ.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        omp = 0
+    return max(1, min(n, omp) if omp > 0 else n)
+
+
+def capture_outputs(out):
+    """Host copies (float32, or float64 where the engine returned float64) of what one pass returned, for --dump-outputs."""
+    return {k: v.detach().cpu().numpy().astype(np.float64 if v.dtype == torch.float64 else np.float32) for k, v in out.items()}
+
+
+def dump_outputs(outputs, d):
+    """Write `outputs` as d/<name>.npy.  Over DUMP_LIMIT_BYTES in all, every array keeps the same rows of its batch axis: a sorted
+    sample drawn with a fixed seed, so two runs with the same arguments write the same rows."""
+    B = next(iter(outputs.values())).shape[0]
+    per_row = sum(a.nbytes // max(a.shape[0], 1) for a in outputs.values())
+    keep = max(1, min(B, DUMP_LIMIT_BYTES // max(per_row, 1)))
+    rows = None if keep == B else np.sort(np.random.default_rng(0).choice(B, keep, replace=False))
+    os.makedirs(d, exist_ok=True)
+    for k, a in outputs.items():
+        np.save(os.path.join(d, f"{k}.npy"), a if rows is None else a[rows])
+    what = f"rows {keep} of {B} (seeded sample)" if rows is not None else f"all {B} rows"
+    print(f"bench.py: wrote {', '.join(sorted(outputs))} to {d} ({what})", file=sys.stderr)
 
 
 def csrc_sha():
@@ -123,13 +161,14 @@ def cpu_baseline(weights, material, n_obj, kw, T=10, gpu_out=None):
     trajectory the engine's result is held against: `drift` = max |engine - oracle| over those samples after the T steps, per arithmetic mode
     (`gpu_out`: mode -> engine state_seqs as numpy) — per STEP on identical graphs the deviation is <= 1e-5 (tests); over a rollout a top-k
     near-tie can pick another neighbour and the trajectories part (profiles/r05_rollout_drift.txt), which is what this number shows.
-    A host with few threads runs fewer samples and, below 32 threads, fewer steps (then no drift is reported)."""
+    A host with few threads runs fewer samples and, below 16 threads, fewer steps (then no drift is reported); the threads counted are the ones
+    this process may use (host_threads()), so the leg takes about T x 3.3 s wherever it runs."""
     from oracle import ag_oracle as ago
     os.environ.setdefault("OMP_WAIT_POLICY", "passive")      # idle OpenMP threads sleep instead of spinning beside torch's own pool
-    cores = os.cpu_count() or 1
+    cores = host_threads()
     B = 256
     bsz = max(1, min(cores, B))
-    steps = T if cores >= 32 else 2
+    steps = T if cores >= 16 else 2
     state, act = synth.make_mpc_inputs(material, n_obj, B, seed=0, len_lo=steps, len_hi=steps + 0.9, **kw)
     act = act[:bsz]
     task = configs.task_config(material)
@@ -161,7 +200,7 @@ def cpu_baseline_dense(weights, material, n_obj, kw, seconds_budget=8.0):
     to one-hots as graph.py:152-155 returns them) + forward + state shift.  Bounded sample: the batch the one-hots let fit."""
     from oracle import ag_oracle as ago
     from oracle.torch_dense import dense_forward, one_hots
-    cores = os.cpu_count() or 1
+    cores = host_threads()
     mm = synth.MATERIALS[material]
     bsz = 4 if n_obj <= 1000 else 1
     g = synth.make_graph_inputs(material, n_obj, bsz, seed=0, **kw)
@@ -240,16 +279,17 @@ class Engine:
             dist.barrier()
         torch.cuda.synchronize()
 
-    def run(self, batch, T, precision, streams, steps, warmup, profile=True, global_batch=None, tag="main", keep=False):
+    def run(self, batch, T, precision, streams, steps, warmup, profile=True, global_batch=None, tag="main", keep=False, dump=False):
         """`batch` graphs per GPU (weak scaling) or, with `global_batch`, that many graphs split over the ranks (strong scaling:
         BASELINE configs[3] = cloth batch 512 over 8 GPUs).  `tag`: name of this run's wall-clock legs; `keep`: return the predicted states
-        (numpy) so that the CPU leg can hold them against the oracle's rollout of the same inputs."""
+        (numpy) so that the CPU leg can hold them against the oracle's rollout of the same inputs; `dump`: return host copies of everything
+        the last timed pass returned (`outputs`, for --dump-outputs)."""
         if tag == "main":          # the headline run is split into its own legs (set-up, warm-up, timed, roofline pass)
-            return self._run(batch, T, precision, streams, steps, warmup, profile, global_batch, tag, keep)
+            return self._run(batch, T, precision, streams, steps, warmup, profile, global_batch, tag, keep, dump)
         with leg(tag):
-            return self._run(batch, T, precision, streams, steps, warmup, profile, global_batch, tag, keep)
+            return self._run(batch, T, precision, streams, steps, warmup, profile, global_batch, tag, keep, dump)
 
-    def _run(self, batch, T, precision, streams, steps, warmup, profile, global_batch, tag, keep):
+    def _run(self, batch, T, precision, streams, steps, warmup, profile, global_batch, tag, keep, dump=False):
         wl = WORKLOADS[self.material]
         sub = (lambda n: leg(f"main_{n}")) if tag == "main" else (lambda n: contextlib.nullcontext())
         B_global = batch * self.world if global_batch is None else global_batch
@@ -290,12 +330,13 @@ class Engine:
         self.model.take_status = take
         status[0] |= int(self.model.take_status())
         assert out["state_seqs"].shape == (B_global, 1, wl["n_obj"], 3) and bool(torch.isfinite(out["state_seqs"]).all())
+        outputs = capture_outputs(out) if dump else None      # before the roofline pass: with copy=False it reuses the gather buffers
         mm = synth.MATERIALS[self.material]
         prm = _lib.RolloutParams(batch, wl["n_obj"] + mm["n_tools"], wl["n_obj"], 1, mm["topk"], 1 if mm["connect_tools_all"] else 0, mm["n_tools"], T, 0, 0.0)
         res = {"B_global": B_global, "dt": dt, "ms_per_step": dt / steps * 1e3, "value": B_global * T * steps / dt,
                "streams": int(self.L.ag_rollout_streams_for(self.h, ctypes.byref(prm))), "timed_s": dt,
                "roofline": None, "roofline_hbm": None, "kernels": None, "model_status": status[0],
-               "out": out["state_seqs"][:, 0].cpu().numpy() if keep else None}
+               "out": out["state_seqs"][:, 0].cpu().numpy() if keep else None, "outputs": outputs}
         if timing:
             res["rank_ms"] = (agdist.elapsed_ms(timing["rollout"]) / steps, agdist.elapsed_ms(timing["gather"]) / steps)
         if profile:
@@ -388,7 +429,7 @@ class DryEngine(Engine):
         if self.world > 1:
             dist.barrier()
 
-    def run(self, batch, T, precision, streams, steps, warmup, profile=True, global_batch=None, tag="main", keep=False):
+    def run(self, batch, T, precision, streams, steps, warmup, profile=True, global_batch=None, tag="main", keep=False, dump=False):
         wl = WORKLOADS[self.material]
         B_global = batch * self.world if global_batch is None else global_batch
         state_np, act_np = synth.make_mpc_inputs(self.material, wl["n_obj"], B_global, seed=0, len_lo=T, len_hi=T + 0.9, **wl["kw"])
@@ -405,7 +446,8 @@ class DryEngine(Engine):
         full = stub_dynamics(state, action)
         assert out["state_seqs"].shape == (B_global, 1, wl["n_obj"], 3) and torch.equal(out["state_seqs"], full["state_seqs"])
         return {"B_global": B_global, "dt": dt, "ms_per_step": dt / steps * 1e3, "value": B_global * T * steps / dt, "roofline": None,
-                "roofline_hbm": None, "kernels": None, "model_status": 0, "rank_ms": (t_roll / steps * 1e3, t_gather / steps * 1e3)}
+                "roofline_hbm": None, "kernels": None, "model_status": 0, "rank_ms": (t_roll / steps * 1e3, t_gather / steps * 1e3),
+                "outputs": capture_outputs(out) if dump else None}
 
 
 def main():
@@ -420,9 +462,14 @@ def main():
                          "= BASELINE configs[3]; overrides --batch")
     ap.add_argument("--weights", default="seed0", help="seed0 (reference default init) or a trained set of tools/gen_trained.py, e.g. trained_rope")
     ap.add_argument("--rollout-steps", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true", help="skip the per-kernel HIP-event roofline pass")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra workloads (f32 mode, granular-2k, cloth-4k)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the per-kernel roofline pass, the extra workloads and the CPU baselines "
+                         "(a plain run only sets up, warms up, times --steps passes and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed pass returned as DIR/<name>.npy (float32; at most 64 MB, a seeded sample of the batch beyond)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: skip the per-kernel HIP-event roofline pass")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the extra workloads (f32 mode, granular-2k, cloth-4k)")
     ap.add_argument("--precision", default="fast", choices=sorted(PRECISIONS),
                     help="engine arithmetic mode: f32 = exact fp32 MFMA, bf16x3 = split-bf16, fast (default) = bf16x3 node stacks + fp16 edge stack "
                          "with fp8 corrections + q16 table; all three hold the 1e-4 gate at any motion size with model_status 0 "
@@ -434,6 +481,10 @@ def main():
     ap.add_argument("--cu-split", type=int, default=None,
                     help="CUs (multiple of 8) of the MFMA partition of the CU-partitioned rollout, 0 = off (default: the engine's own choice)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:
+        args.no_profile = args.no_extra = args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -467,7 +518,9 @@ def main():
     T = args.rollout_steps
     want_drift = world == 1 and not args.no_cpu_baseline and not args.dry_run and args.global_batch is None and args.batch == 256
     r = eng.run(args.batch, T, args.precision, args.streams, args.steps, args.warmup, profile=not args.no_profile,
-                global_batch=args.global_batch, keep=want_drift)
+                global_batch=args.global_batch, keep=want_drift, dump=args.dump_outputs is not None and rank == 0)
+    if r["outputs"] is not None:
+        dump_outputs(r.pop("outputs"), args.dump_outputs)
     gpu_out = {args.precision: r.get("out")}
     per_gpu = -(-r["B_global"] // world)
 

@@ -214,3 +214,38 @@ def test_bench_dry_run_world8_weak_scaling_and_mpc_contract():
     m = _torchrun("bench_mpc.py", 8, ["--steps", "1", "--warmup", "1", "--samples", "1024", "--particles", "50"])
     assert m["n_gpus"] == 8 and m["scaling"] == "strong" and m["higher_is_better"] is False and m["unit"] == "ms"
     assert m["config"]["samples"] == 1024 and m["config"]["parallelism"] == "samples/8" and m["value"] > 0
+
+
+def test_bench_dry_run_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR`: rank 0 alone writes what the last timed pass returned (the all-gathered result) as float32 .npy files;
+    the inputs are seeded, so a 2-rank run and a 1-rank run of the same global batch write the same arrays, and `--steps` sets the
+    number of timed passes behind `ms_per_step`."""
+    import numpy as np
+    a, b = tmp_path / "two", tmp_path / "one"
+    d = _torchrun("bench.py", 2, ["--steps", "3", "--warmup", "1", "--batch", "4", "--dump-outputs", str(a)])
+    assert d["steps"] == 3 and abs(d["value"] * d["ms_per_step"] / 1e3 - 8 * 10) <= 1e-6 * 8 * 10
+    assert "extra" not in d and "cpu_baseline" not in d and d["roofline"] is None
+    _torchrun("bench.py", 1, ["--steps", "1", "--warmup", "0", "--batch", "8", "--dump-outputs", str(b)])
+    assert sorted(os.listdir(a)) == sorted(os.listdir(b)) == ["action_seqs.npy", "state_seqs.npy"]
+    for name in ("action_seqs.npy", "state_seqs.npy"):
+        x, y = np.load(a / name), np.load(b / name)
+        assert x.dtype == np.float32 and x.shape[0] == 8 and np.array_equal(x, y)
+
+
+def test_bench_dump_outputs_samples_rows_past_the_limit(tmp_path, monkeypatch):
+    """Past the size limit every array keeps the same rows of its batch axis, a sorted sample drawn with a fixed seed."""
+    import numpy as np
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0")       # what importing bench.py sets; undone after this test
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * (12 + 4) * 4)      # room for 10 rows of both arrays below
+    B = 37
+    outs = {"state_seqs": np.arange(B * 12, dtype=np.float32).reshape(B, 1, 4, 3), "action_seqs": np.arange(B * 4, dtype=np.float32).reshape(B, 1, 4)}
+    bench.dump_outputs(outs, str(tmp_path / "a"))
+    bench.dump_outputs(outs, str(tmp_path / "b"))
+    s, act = np.load(tmp_path / "a" / "state_seqs.npy"), np.load(tmp_path / "a" / "action_seqs.npy")
+    assert s.shape == (10, 1, 4, 3) and act.shape == (10, 1, 4)
+    rows = s[:, 0, 0, 0].astype(np.int64) // 12
+    assert (np.diff(rows) > 0).all() and np.array_equal(act[:, 0, 0].astype(np.int64) // 4, rows)
+    assert np.array_equal(s, np.load(tmp_path / "b" / "state_seqs.npy"))
+    bench.dump_outputs({k: v[:5] for k, v in outs.items()}, str(tmp_path / "c"))        # under the limit: everything
+    assert np.array_equal(np.load(tmp_path / "c" / "state_seqs.npy"), outs["state_seqs"][:5])

@@ -58,7 +58,7 @@ def test_bench_entrypoint_under_torchrun_single_rank():
     import json
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
            "--master-port", str(29900 + os.getpid() % 90), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-           "--batch", "32", "--no-cpu-baseline", "--no-extra"]
+           "--batch", "32", "--full", "--no-cpu-baseline", "--no-extra"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-4000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -92,7 +92,7 @@ def test_bench_strong_scaling_global_batch_two_ranks_over_gloo():
     env = dict(os.environ, AG_DIST_BACKEND="gloo")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(29600 + os.getpid() % 90), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--material", "cloth", "--global-batch", "6", "--rollout-steps", "3", "--no-cpu-baseline"]
+           "--material", "cloth", "--global-batch", "6", "--rollout-steps", "3", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-4000:]
     lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
@@ -100,6 +100,33 @@ def test_bench_strong_scaling_global_batch_two_ranks_over_gloo():
     line = json.loads(lines[0])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["config"]["global_batch"] == 6 and line["value"] > 0
     assert "3/GPU" in line["config"]["workload"] and line["roofline"]["frac"] > 0 and line["roofline_hbm"]["frac"] > 0
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain `bench.py --gpus 1` run, as every change's benchmark is run: the headline keys only (no roofline pass, extra workloads or
+    CPU baseline), exactly `--steps` timed passes behind `ms_per_step`, and with `--dump-outputs` what the last timed pass returned —
+    float32, the same bits in two runs with the same arguments (what makes two builds comparable output for output)."""
+    import json
+    import numpy as np
+    outs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "32",
+               "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-4000:]
+        lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["ms_per_step"] > 0
+        assert abs(line["value"] * line["ms_per_step"] / 1e3 - 32 * 10) <= 1e-6 * 32 * 10, "value = batch x rollout steps / ms_per_step"
+        assert line["unit"] == "graph-steps/s" and line["higher_is_better"] is True and line["dtype"] == "f16+fp8corr+bf16x3"
+        assert line["config"]["model_status"] == 0 and line["roofline"] is None and line["kernels"] is None
+        assert "extra" not in line and "cpu_baseline" not in line
+        outs.append({k: np.load(d / f"{k}.npy") for k in ("state_seqs", "action_seqs")})
+    assert outs[0]["state_seqs"].shape == (32, 1, 1000, 3) and outs[0]["action_seqs"].shape[0] == 32
+    assert all(a.dtype == np.float32 for a in outs[0].values()) and np.isfinite(outs[0]["state_seqs"]).all()
+    assert all(np.array_equal(outs[0][k], outs[1][k]) for k in outs[0]), "same arguments, same outputs"
 
 
 def test_mpc_bench_two_ranks_one_gpu_over_gloo():

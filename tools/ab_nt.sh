@@ -4,7 +4,7 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 one() { # tag lib extra-args...
   tag=$1; so=$2; shift 2
-  AG_LIB_PATH=$PWD/$so python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra "$@" 2>/dev/null | python -c "
+  AG_LIB_PATH=$PWD/$so python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('%-14s %8.0f graph-steps/s  ' % ('$tag', d['value']) + '  '.join('%s %.4f' % (n[:6], v['ms_per_launch']) for n,v in d['kernels'].items()))"

@@ -5,7 +5,7 @@ run() { # label, env...
   label=$1; shift
   for mat in rope granular cloth; do
     b=256; t=10; [ $mat = granular ] && b=128; [ $mat = cloth ] && { b=64; t=20; }
-    env "$@" python bench.py --material $mat --batch $b --rollout-steps $t --steps 10 --warmup 3 --no-cpu-baseline --no-extra 2>/dev/null | python -c "
+    env "$@" python bench.py --material $mat --batch $b --rollout-steps $t --steps 10 --warmup 3 --full --no-cpu-baseline --no-extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('$label', '$mat', round(d['value'],1), {k:round(v['ms_per_launch'],4) for k,v in d['kernels'].items()})"

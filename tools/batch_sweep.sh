@@ -3,7 +3,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}; cd $REPO
 MAT=$1; T=$2; BATCHES=$3; shift 3
 for b in $BATCHES; do
-  python bench.py --material $MAT --batch $b --rollout-steps $T --steps 3 --warmup 1 --no-cpu-baseline --no-extra "$@" 2>/dev/null | python -c "
+  python bench.py --material $MAT --batch $b --rollout-steps $T --steps 3 --warmup 1 --full --no-cpu-baseline --no-extra "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); b=$b
 k=d['kernels']

@@ -3,10 +3,10 @@
 # Optional: ab/libexp.so (tools/ab_build.sh exp="-DAG_EXPERIMENTS") for the segment-reduce experiments' PMC table.
 REPO=${GRAFT_REPO_ROOT:-/root/repo}; cd $REPO; EV=$REPO/gpurun_out/ev; rm -rf $EV; mkdir -p $EV
 python -c "import torch" 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $EV/r03_bench.json 2> $EV/bench.err
-python bench.py --steps 5 --warmup 2 --streams 1 --no-cpu-baseline --no-extra > $EV/r03_bench_1stream.json 2>> $EV/bench.err
-python bench.py --steps 5 --warmup 2 --weights trained_rope --no-cpu-baseline --no-extra > $EV/r03_bench_trained_weights.json 2>> $EV/bench.err
-AG_NODE_DEDUP=0 python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > $EV/r03_bench_no_dedup.json 2>> $EV/bench.err
+python bench.py --full --steps 20 --warmup 5 > $EV/r03_bench.json 2> $EV/bench.err
+python bench.py --steps 5 --warmup 2 --streams 1 --full --no-cpu-baseline --no-extra > $EV/r03_bench_1stream.json 2>> $EV/bench.err
+python bench.py --steps 5 --warmup 2 --weights trained_rope --full --no-cpu-baseline --no-extra > $EV/r03_bench_trained_weights.json 2>> $EV/bench.err
+AG_NODE_DEDUP=0 python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra > $EV/r03_bench_no_dedup.json 2>> $EV/bench.err
 {
 echo "# bench_mpc.py on one MI355X (precision fast): BASELINE configs[4] and the reference planner's shipped shape (config/planning/rope.yaml:28-42)"
 for args in "" "--particles 200 --samples 20000" "--particles 200 --samples 20000 --chunk 500" "--particles 200 --samples 500" "--particles 100 --samples 500"; do
@@ -25,7 +25,7 @@ python tools/dyn_err.py > $EV/r03_dyn_err.txt 2>/dev/null
 cd /tmp && export TMPDIR=/tmp
 for m in "rope 256 10" "granular 128 10" "cloth 64 20"; do set -- $m
   rm -rf $EV/trace1
-  timeout 300 rocprofv3 --kernel-trace --stats -d $EV/trace1 -o t -- python $REPO/bench.py --material $1 --batch $2 --rollout-steps $3 --steps 5 --warmup 2 --streams 1 --no-cpu-baseline --no-extra > $EV/r03_bench_1stream_traced_$1.json 2>/dev/null
+  timeout 300 rocprofv3 --kernel-trace --stats -d $EV/trace1 -o t -- python $REPO/bench.py --material $1 --batch $2 --rollout-steps $3 --steps 5 --warmup 2 --streams 1 --full --no-cpu-baseline --no-extra > $EV/r03_bench_1stream_traced_$1.json 2>/dev/null
   python $REPO/tools/rocpd_summary.py trace $(find $EV/trace1 -name "*.db" | head -1) > $EV/r03_kernel_trace_stats_1stream_$1.txt
 done
 rm -rf $EV/trace1

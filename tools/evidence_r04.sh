@@ -3,8 +3,8 @@
 #   tools/evidence_r04.sh [quick]      quick: skip the MPC / training / batch-sweep legs
 REPO=${GRAFT_REPO_ROOT:-/root/repo}; cd $REPO; EV=$REPO/gpurun_out/ev4; rm -rf $EV; mkdir -p $EV
 python -c "import torch" 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $EV/r04_bench.json 2> $EV/bench.err
-python bench.py --steps 5 --warmup 2 --streams 1 --no-cpu-baseline --no-extra > $EV/r04_bench_1stream.json 2>> $EV/bench.err
+python bench.py --full --steps 20 --warmup 5 > $EV/r04_bench.json 2> $EV/bench.err
+python bench.py --steps 5 --warmup 2 --streams 1 --full --no-cpu-baseline --no-extra > $EV/r04_bench_1stream.json 2>> $EV/bench.err
 python tools/fwd_err.py > $EV/r04_fwd_err.txt 2>/dev/null
 python tools/dyn_err.py > $EV/r04_dyn_err.txt 2>/dev/null
 python tools/stress_repeat.py 300 > $EV/r04_stress_repeat.txt 2>/dev/null
@@ -23,7 +23,7 @@ fi
 cd /tmp && export TMPDIR=/tmp
 for m in "rope 256 10" "granular 128 10" "cloth 64 20"; do set -- $m
   rm -rf $EV/trace1
-  timeout 300 rocprofv3 --kernel-trace --stats -d $EV/trace1 -o t -- python $REPO/bench.py --material $1 --batch $2 --rollout-steps $3 --steps 5 --warmup 2 --streams 1 --no-cpu-baseline --no-extra > $EV/r04_bench_1stream_traced_$1.json 2>/dev/null
+  timeout 300 rocprofv3 --kernel-trace --stats -d $EV/trace1 -o t -- python $REPO/bench.py --material $1 --batch $2 --rollout-steps $3 --steps 5 --warmup 2 --streams 1 --full --no-cpu-baseline --no-extra > $EV/r04_bench_1stream_traced_$1.json 2>/dev/null
   python $REPO/tools/rocpd_summary.py trace $(find $EV/trace1 -name "*.db" | head -1) > $EV/r04_kernel_trace_stats_1stream_$1.txt
 done
 rm -rf $EV/trace1
@@ -35,5 +35,5 @@ rm -rf $EV/pmc_sq
 timeout 1500 python $REPO/tools/pmc_traffic.py --out $EV/pmc_traffic.json > /dev/null 2>&1
 # the bench line once more, now that the traffic file matches the sources being run (bench.py quotes it only then)
 cp $EV/pmc_traffic.json $REPO/profiles/pmc_traffic.json
-cd $REPO && python bench.py --steps 20 --warmup 5 > $EV/r04_bench.json 2>> $EV/bench.err
+cd $REPO && python bench.py --full --steps 20 --warmup 5 > $EV/r04_bench.json 2>> $EV/bench.err
 ls -la $EV

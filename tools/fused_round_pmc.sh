@@ -7,7 +7,7 @@ echo "# per-launch ms of one C2 forward (tools/time_forward.py; with fuse 2 the 
 for f in 0 2; do echo -n "AG_FUSE_AGG=$f  "; AG_FUSE_AGG=$f python tools/time_forward.py 2 20 2>&1 | tail -1; done
 echo "# bench.py (two rollout streams), graph-steps/s"
 for i in 1 2; do for f in 0 2; do
-  AG_FUSE_AGG=$f python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra 2>/dev/null | python -c "
+  AG_FUSE_AGG=$f python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 print('AG_FUSE_AGG=$f %8.0f  ' % d['value'] + '  '.join('%s %.4f' % (n[:9], v['ms_per_launch']) for n,v in d['kernels'].items()))"
