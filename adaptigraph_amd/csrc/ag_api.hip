@@ -643,6 +643,33 @@ int ag_chamfer_masked(const float *x, const uint8_t *x_mask, const float *y, con
     return chamfer_common("ag_chamfer_masked", x, x_mask, y, y_mask, B, N, M, y_batched, out, stream);
 }
 
+int ag_chamfer_fwd_idx(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched,
+                       float *out, int32_t *idx_x, int32_t *idx_y, ag_stream_t stream)
+{
+    const char *who = "ag_chamfer_fwd_idx";
+    if (!x || !y || !out || !idx_x || !idx_y) return fail(AG_ERR_ARG, "%s: null argument", who);
+    if ((x_mask == nullptr) != (y_mask == nullptr)) return fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    if (B < 1 || N < 1 || M < 1) return fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (ag_launch_chamfer_idx(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, idx_x, idx_y, static_cast<hipStream_t>(stream)) != 0)
+        return fail(AG_ERR_ARG, "%s: N + M = %d exceeds the LDS-resident limit (12800 points)", who, N + M);
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_chamfer_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x, const int32_t *idx_y,
+                        const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy, ag_stream_t stream)
+{
+    const char *who = "ag_chamfer_backward";
+    if (!x || !y || !idx_x || !idx_y || !grad_out || !gx) return fail(AG_ERR_ARG, "%s: null argument", who);
+    if ((x_mask == nullptr) != (y_mask == nullptr)) return fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    if (B < 1 || N < 1 || M < 1) return fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (ag_launch_chamfer_backward(x, x_mask, y, y_mask, idx_x, idx_y, grad_out, B, N, M, y_batched ? 1 : 0, gx, gy,
+                                   static_cast<hipStream_t>(stream)) != 0)
+        return fail(AG_ERR_ARG, "%s: N + M = %d exceeds the LDS-resident limit (12800 points)", who, N + M);
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 int ag_gather_rows(const float *x, const int32_t *idx, float *out, int64_t n_out, int D, ag_stream_t stream)
 {
     if (n_out < 0 || D < 1) return fail(AG_ERR_ARG, "ag_gather_rows: bad sizes n_out=%lld D=%d", (long long)n_out, D);

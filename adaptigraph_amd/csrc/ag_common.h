@@ -531,3 +531,7 @@ void ag_launch_weight_grads(int n_layers, const float *const *dz, const int *dz_
                             hipStream_t s);
 int ag_launch_chamfer(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,
                       int y_batched, float *out, hipStream_t s);
+int ag_launch_chamfer_idx(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,
+                          int y_batched, float *out, int *idx_x, int *idx_y, hipStream_t s);
+int ag_launch_chamfer_backward(const float *x, const unsigned char *xmask, const float *y, const unsigned char *ymask, const int *idx_x,
+                               const int *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy, hipStream_t s);

@@ -2,7 +2,7 @@
 
 `dynamics(state, action, model, device, ppm_optimizer, physics_param=None)` (:11-205) and
 `dynamics_masked(state_init, state_mask, action, model, device, ppm_optimizer, physics_param=None)` (:208-399)
-keep the reference signatures and return dicts.  The per-sample set-up (tool key-points from the decoded
+keep the reference signatures and return dicts; `dynamics_differentiable` is `dynamics` under autograd (gradient planning).  The per-sample set-up (tool key-points from the decoded
 action) is a handful of tiny device tensor ops; the inner loop — edges -> GNN forward -> record-on-repeat ->
 tool advance -> history shift -> edge rebuild — is one `ag_rollout` call with no host synchronisation
 (the reference syncs three times per step: truncate_graph, n_rels.max().item(), pad_torch).
@@ -240,6 +240,74 @@ def dynamics(state, action, model, device, ppm_optimizer, physics_param=None):
             seq[:, li] = res
     _strict_status(model, device)
     return {"state_seqs": seq, "action_seqs": decoded}
+
+
+def _frozen_view(model):
+    """The parameters of a DynamicsPredictor (or TrainableDynamicsPredictor) DETACHED, in the attribute layout
+    TrainableDynamicsPredictor.forward reads: the differentiable rollout optimises actions / physics, never the weights, so no weight
+    gradient is ever formed (the chain / linear backward passes skip it when no parameter asks for one)."""
+    from types import SimpleNamespace as NS
+    lin = lambda m: NS(weight=m.weight.detach(), bias=m.bias.detach())      # noqa: E731
+    mlp = lambda blk: NS(model={i: lin(blk.model[i]) for i in (0, 2, 4)})   # noqa: E731
+    d = model.non_rigid_predictor
+    return NS(nf_effect=model.nf_effect, model_config=model.model_config, motion_clamp=model.motion_clamp, fused_dense=True,
+              particle_encoder=mlp(model.particle_encoder), relation_encoder=mlp(model.relation_encoder),
+              relation_propagator=NS(linear=lin(model.relation_propagator.linear)), particle_propagator=NS(linear=lin(model.particle_propagator.linear)),
+              non_rigid_predictor=NS(linear_0=lin(d.linear_0), linear_1=lin(d.linear_1), linear_2=lin(d.linear_2)))
+
+
+def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics_param=None):
+    """`dynamics` under autograd: the same signature, output dict and semantics (forward_dynamics.py:12-205 without @torch.no_grad,
+    including the .detach() of the object state between look-ahead pushes, the tool height from min y, the per-sample action_repeat
+    record and gripper_enable), with gradients to `action` (x, z, theta; the push length only counts steps) and to physics_param
+    tensors that require grad.  Model weights are used detached.
+
+    Per model step: the HIP radius / top-k edge builder under no_grad, `train_ops.EdgeViews` over its edges, then
+    TrainableDynamicsPredictor.forward (HIP gather / segment-sum kernels and fused MFMA chains, forward and backward).
+    Cost: one host read per model step (the edge count of EdgeViews) plus one per look-ahead push (its step count), and memory of
+    O(steps x saved activations): meant for planning batches of tens to a few hundred samples, not the 20 000 of an MPPI sweep,
+    which `dynamics` serves without autograd."""
+    from .graph import build_edges
+    from .train_model import TrainableDynamicsPredictor
+    from .train_ops import EdgeViews
+
+    task = ppm_optimizer.task_config
+    n_his, push_length, ratio = task["n_his"], task["push_length"], task["sim_real_ratio"]
+    state = state.to(device, torch.float32)
+    action = action.to(device, torch.float32)
+    bsz, n_look = action.shape[0], action.shape[1]
+    decoded, repeat = decode_action(action, push_length=push_length)
+    n_obj, n_t = state.shape[0], ppm_optimizer.eef_num
+    attrs, p_instance, mask, tool_mask, _ = _constants(bsz, n_obj, n_t, task["max_n"], device)
+    phys = _physics(ppm_optimizer, physics_param, bsz, device)
+    phys_key = ppm_optimizer.material + "_physics_param"
+    view = _frozen_view(model)
+    raise_by = 0.01 * ratio if task["gripper_enable"] else 0.0
+    obj_still = torch.zeros((bsz, n_obj, 3), device=device)
+    max_steps = repeat.max(dim=0).values.tolist()
+    seqs = []
+    obj = state[None].expand(bsz, n_obj, 3)
+    for li in range(n_look):
+        if li > 0:
+            obj = seqs[li - 1].detach()                                               # forward_dynamics.py:38
+        y = obj[:, :, 1].min(dim=1).values
+        eef, dlt, _ = _place_tool(task, decoded[:, li], action[:, li, 2], y, device)
+        states = torch.cat([obj[:, None].expand(bsz, n_his, n_obj, 3), eef[:, None].expand(bsz, n_his, n_t, 3)], dim=2)
+        delta = torch.cat([obj_still, dlt], dim=1)
+        rec = torch.zeros((bsz, n_obj, 3), device=device)
+        for ai in range(1, 1 + int(max_steps[li])):
+            with torch.no_grad():
+                csr = build_edges(states[:, -1].detach(), ppm_optimizer.adj_thresh, mask, tool_mask, task["topk"], task["connect_tools_all"],
+                                  "batch", max_tools=n_t)
+            pred, _ = TrainableDynamicsPredictor.forward(view, states, attrs, csr, None, p_instance, action=delta, edge_views=EdgeViews(csr),
+                                                         **{phys_key: phys})
+            rec = torch.where((repeat[:, li] == ai)[:, None, None], pred, rec)
+            tool = states[:, -1, n_obj:] + delta[:, n_obj:]
+            y_cur = pred[:, :, 1].min(dim=1).values + raise_by
+            tool = torch.stack([tool[..., 0], y_cur[:, None].expand(bsz, n_t), tool[..., 2]], dim=-1)
+            states = torch.cat([states[:, 1:], torch.cat([pred, tool], dim=1)[:, None]], dim=1)
+        seqs.append(rec)
+    return {"state_seqs": torch.stack(seqs, dim=1), "action_seqs": decoded}
 
 
 @torch.no_grad()

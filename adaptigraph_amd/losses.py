@@ -11,11 +11,60 @@ from . import _lib
 from .graph import _require_gpu, _stream_ptr
 
 
+def _needs_grad(*ts):
+    return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
+
+
+class _Chamfer(torch.autograd.Function):
+    """chamfer with a backward: `ag_chamfer_fwd_idx` (the same value bits as ag_chamfer / ag_chamfer_masked, plus the nearest-neighbour index
+    of every point) and `ag_chamfer_backward` (gather form, no atomics: the gradient is the same bits on every call).  x (B,N,3) and y (B|1,M,3)
+    fp32 contiguous on one GPU, xm / ym (B,N) / (B|1,M) u8 or both None.  A broadcast y (B > 1, one cloud) gets the sum of the per-sample
+    gradients in ascending sample order."""
+
+    @staticmethod
+    def forward(ctx, x, y, xm, ym):
+        B, N, M = x.shape[0], x.shape[1], y.shape[1]
+        y_batched = 1 if (y.shape[0] == B and B > 1) else 0
+        out = torch.empty(B, dtype=torch.float32, device=x.device)
+        idx_x = torch.empty((B, N), dtype=torch.int32, device=x.device)
+        idx_y = torch.empty((B, M), dtype=torch.int32, device=x.device)
+        with torch.cuda.device(x.device):
+            rc = _lib.lib().ag_chamfer_fwd_idx(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
+                                               ym.data_ptr() if ym is not None else None, B, N, M, y_batched, out.data_ptr(),
+                                               idx_x.data_ptr(), idx_y.data_ptr(), _stream_ptr(x.device))
+        _lib.check(rc, "ag_chamfer_fwd_idx")
+        ctx.save_for_backward(x, y, idx_x, idx_y)
+        ctx.masks, ctx.y_batched = (xm, ym), y_batched
+        ctx.mark_non_differentiable(idx_x, idx_y)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        x, y, idx_x, idx_y = ctx.saved_tensors
+        xm, ym = ctx.masks
+        B, N, M = x.shape[0], x.shape[1], y.shape[1]
+        want_y = ctx.needs_input_grad[1]
+        g = grad_out.contiguous().float()
+        gx = torch.empty_like(x)
+        gy = torch.empty((B, M, 3), dtype=torch.float32, device=x.device) if want_y else None      # (a broadcast y: per-sample rows, summed into row 0)
+        with torch.cuda.device(x.device):
+            rc = _lib.lib().ag_chamfer_backward(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
+                                                ym.data_ptr() if ym is not None else None, idx_x.data_ptr(), idx_y.data_ptr(), g.data_ptr(),
+                                                B, N, M, ctx.y_batched, gx.data_ptr(), gy.data_ptr() if want_y else None, _stream_ptr(x.device))
+        _lib.check(rc, "ag_chamfer_backward")
+        if want_y and y.shape[0] != B:
+            gy = gy[:1]
+        return gx, gy, None, None
+
+
 def chamfer(x, y):
-    """x (B,N,3), y (B or 1,M,3) -> (B,)  mean_m min_n ||x-y|| + mean_n min_m ||x-y||   (losses.py:4-10)."""
+    """x (B,N,3), y (B or 1,M,3) -> (B,)  mean_m min_n ||x-y|| + mean_n min_m ||x-y||   (losses.py:4-10).
+    Differentiable in x and y when grad mode is on and either requires grad (same value bits either way)."""
     _require_gpu(x, "x")
     assert x.dim() == 3 and y.dim() == 3 and x.shape[2] == 3 and y.shape[2] == 3
     assert y.shape[0] in (1, x.shape[0])
+    if _needs_grad(x, y):
+        return _Chamfer.apply(x.contiguous().float(), y.to(x.device).contiguous().float(), None, None)
     x = x.contiguous().float()
     y = y.to(x.device).contiguous().float()
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
@@ -35,6 +84,8 @@ def mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask
     xm = state_pred_mask.to(dev).ne(0).to(torch.uint8).contiguous()
     ym = state_real_mask.to(dev).ne(0).to(torch.uint8).contiguous()
     assert x.dim() == 3 and y.dim() == 3 and y.shape[0] == x.shape[0] and xm.shape == x.shape[:2] and ym.shape == y.shape[:2]
+    if _needs_grad(state_pred, state_real):      # (sys-id by gradient: differentiable in both clouds, same value bits)
+        return _Chamfer.apply(x, y, xm, ym)
     out = torch.empty(x.shape[0], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         rc = _lib.lib().ag_chamfer_masked(x.data_ptr(), xm.data_ptr(), y.data_ptr(), ym.data_ptr(), x.shape[0], x.shape[1],

@@ -135,6 +135,53 @@ class Planner:
                 "best_model_output": best["best_model_output"], "best_eval_output": best["best_eval_output"]}
 
 
+class GradientPlanner(Planner):
+    """The reference Planner's 'GD' branch (src/planning/real_world/planner.py:212-223, 279-310): Adam on the sampled action sequences
+    themselves, `-mean(reward)` differentiated through the rollout and the cost.  The same config keys as `Planner` (planner_type is not
+    read) plus `lr` (default 1e-3, planner.py:114); `trajectory_optimization(state_cur, act_seq)` returns the same result dict.
+
+    `model_rollout_fn` must be differentiable in the actions for the model to steer the plan:
+    `partial(adaptigraph_amd.forward_dynamics.dynamics_differentiable, model=..., device=..., ppm_optimizer=...)`.  With the no-grad
+    `dynamics` only the cost terms that read the actions directly (the penalties) carry a gradient, exactly as in the reference.  A NaN
+    gradient raises FloatingPointError (the reference prints and exits)."""
+
+    def __init__(self, config):
+        super().__init__(dict(config, planner_type="GD"))
+        self.lr = config.get("lr", 1e-3)
+
+    def trajectory_optimization(self, state_cur, act_seq):
+        assert isinstance(state_cur, torch.Tensor) and isinstance(act_seq, torch.Tensor)
+        assert act_seq.shape == (self.n_look_ahead, self.action_dim)
+        with torch.no_grad():
+            act_seqs = self.sample_action_sequences(act_seq)
+        act_seqs = act_seqs.detach().clone().requires_grad_()
+        optimizer = torch.optim.Adam([act_seqs], lr=self.lr, betas=(0.9, 0.999))
+        model_outputs, eval_outputs = [], []
+        reward = None
+        for _ in range(self.n_update_iter):
+            assert act_seqs.shape == (self.n_sample, self.n_look_ahead, self.action_dim)
+            model_out = self.model_rollout(state_cur, act_seqs)
+            eval_out = self.evaluate_traj(model_out["state_seqs"], act_seqs, state_cur=state_cur)
+            reward = eval_out["reward_seqs"]
+            optimizer.zero_grad()
+            (-torch.mean(reward)).backward()
+            if act_seqs.grad is not None and bool(torch.isnan(act_seqs.grad).any()):
+                raise FloatingPointError("GradientPlanner: NaN in the gradient of the reward w.r.t. the action sequences")
+            optimizer.step()
+            self.clip_action_sequences(act_seqs)
+            if self.verbose:
+                model_outputs.append(model_out)
+                eval_outputs.append(eval_out)
+        best_seq = act_seqs[torch.argmax(reward)]         # the last iteration's rewards, the sequences after its step (planner.py:302)
+        best_model_out = best_eval_out = None
+        if self.rollout_best:
+            best_model_out = self.model_rollout(state_cur, best_seq[None])
+            best_eval_out = self.evaluate_traj(best_model_out["state_seqs"], best_seq[None], state_cur=state_cur)
+        return {"act_seq": best_seq, "model_outputs": model_outputs if self.verbose else None,
+                "eval_outputs": eval_outputs if self.verbose else None, "best_model_output": best_model_out,
+                "best_eval_output": best_eval_out}
+
+
 class MPPIPlanner:
     """Minimal planner with the reference Planner's MPPI branch (planner.py:38-326 keeps many unrelated modes)."""
 

@@ -259,6 +259,8 @@ class _FusedChain(torch.autograd.Function):
             rc = _lib.lib().ag_train_chain(code, 1, ctx.prec, xin.data_ptr(), ctx.bwd.data_ptr(), _ptr_array(ys), dy.data_ptr(), _ptr_array(dzs),
                                            dx.data_ptr(), rows, ctx.d_in, _stream_ptr(dev))
         _lib.check(rc, "ag_train_chain(backward)")
+        if not any(ctx.needs_input_grad[2:]):      # no parameter wants a gradient (a rollout differentiated w.r.t. its inputs only)
+            return (None, dx[:rows, : ctx.d_in]) + (None,) * (2 * n)
         # dW_l = dz_l^T y_{l-1}, db_l = column sums of dz_l: all layers in two launches (row-slab split-K on the fp32 MFMA,
         # fixed-order reduction) — a 150 x 150 output over 10^4..10^5 rows runs on 25 workgroups as a library GEMM
         out = weight_grads(dzs, [xin] + ys[:-1], [s[1] for s in ctx.shapes], rows, ctx.params)
@@ -402,6 +404,8 @@ class _Linear(torch.autograd.Function):
     def backward(ctx, g):
         x, W = ctx.saved_tensors
         g = g.contiguous()
+        if not any(ctx.needs_input_grad[1:]):      # frozen weight and bias: the input gradient only
+            return g @ W, None, None
         xs = x if x.stride(1) == 1 else x.contiguous()
         if ctx.params is not None:
             _defer_weight_grads([g], [xs], [W.shape[1]], x.shape[0], ctx.params)
@@ -426,6 +430,8 @@ class _Linear2(torch.autograd.Function):
         g1, g2 = g1.contiguous(), g2.contiguous()
         xs = x if x.stride(1) == 1 else x.contiguous()
         dx = torch.addmm(g1 @ W1, g2, W2)
+        if not any(ctx.needs_input_grad[1:]):      # frozen weights: the input gradient only
+            return dx, None, None
         if ctx.params is not None:
             _defer_weight_grads([g1, g2], [xs, xs], [W1.shape[1], W2.shape[1]], x.shape[0], ctx.params)
             return dx, None, None

@@ -195,6 +195,23 @@ int ag_chamfer(const float *x, const float *y, int B, int N, int M, int y_batche
 int ag_chamfer_masked(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M,
                       int y_batched, float *out, ag_stream_t stream);
 
+/* chamfer with its nearest-neighbour indices: the forward of the differentiable chamfer of src/planning/losses.py:4-24 (the planner's error
+ * term and the sys-id objective under autograd).  Arguments as ag_chamfer / ag_chamfer_masked: x_mask and y_mask are both given or both NULL;
+ * N + M <= 12800.  out (B) is bit-identical to ag_chamfer (masks NULL) / ag_chamfer_masked on the same arguments.  Also writes, as int32:
+ *   idx_x (B,N): for every particle the index of its nearest target point; idx_y (B,M): for every target point the index of its nearest particle.
+ * Ties go to the lowest index; masked-out points (and points of a sample whose other side is empty) get -1. */
+int ag_chamfer_fwd_idx(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched,
+                       float *out, int32_t *idx_x, int32_t *idx_y, ag_stream_t stream);
+
+/* Backward of ag_chamfer_fwd_idx for grad_out (B) = dL/dout, with the indices that call wrote (losses.py:4-24: the min picks one pair per point):
+ *   gx[b,n] = g_b (u(x_n - y_{idx_x[n]}) / Nx + sum_{m: idx_y[m] = n} u(x_n - y_m) / My),   u(v) = v / ||v||, u(0) = 0,
+ * Nx / My the masked-in counts; gy likewise with the roles swapped, computed only when gy is not NULL.  Masked-out points, and every point of a
+ * sample with an empty side (value NaN), get zero.  No atomics: the scatter sums are gathers in ascending index order, bit-reproducible.
+ *   gx (B,N,3).  gy: (B,M,3) for a batched y; for a broadcast y (y_batched == 0) also a (B,M,3) buffer, of which row 0 holds the gradient of
+ *   the shared cloud on return (the per-sample rows summed in ascending b) and rows 1.. are scratch. */
+int ag_chamfer_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x, const int32_t *idx_y,
+                        const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy, ag_stream_t stream);
+
 /* ---- training path: graph pieces of DynamicsPredictor.forward and their adjoints on the CSR adjacency.
  * Plain row-major fp32 tensors of arbitrary feature width D; every reduction runs in a fixed order (no atomics).
  *
