@@ -12,7 +12,6 @@
 // Edges of a receiver are consecutive (reference edge order == CSR order), so the segment reduction is a
 // register accumulation — no atomics, deterministic summation order (ascending sender id, as the reference).
 #include "ag_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -140,9 +139,9 @@ __global__ __launch_bounds__(256, AG_AGG_MINB) void aggregate_half_kernel(AgFwdA
 }
 
 template <bool HSQ, bool SELF>
-void launch_half(const AgFwdArgs &a, dim3 grid, hipStream_t s, bool loop)
+void launch_half(const AgFwdArgs &a, bool agg_q16, dim3 grid, hipStream_t s, bool loop)
 {
-    if (a.agg_q16) {
+    if (agg_q16) {
         if (loop) hipLaunchKernelGGL((aggregate_half_kernel<HSQ, SELF, true, true>), grid, dim3(256), 0, s, a);
         else hipLaunchKernelGGL((aggregate_half_kernel<HSQ, SELF, false, true>), grid, dim3(256), 0, s, a);
         return;
@@ -153,18 +152,18 @@ void launch_half(const AgFwdArgs &a, dim3 grid, hipStream_t s, bool loop)
 
 }  // namespace
 
-void ag_launch_aggregate(const AgFwdArgs &a, hipStream_t s)
+void ag_launch_aggregate(const AgFwdArgs &a, const AgPath &p, int last, hipStream_t s)
 {
     const int nodes = a.B * a.N;
-    static const int env_cap = getenv("AG_AGG_CAP") ? atoi(getenv("AG_AGG_CAP")) : 0;      // A/B: a capped, striding grid on the plain path too
-    const bool loop = a.n_rows_dev != nullptr || env_cap > 0;
-    const int cap = loop ? (env_cap > 0 ? env_cap : 8192) : 0x7fffffff;      // device-side row count: a bounded grid that strides over the blocks that exist
+    const bool loop = a.n_rows_dev != nullptr;
+    const int cap = loop ? 8192 : 0x7fffffff;      // device-side row count: a bounded grid that strides over the blocks that exist
     const bool self = a.self_info != nullptr;
-    if (a.eterm_half) {
+    if (p.q16) {
+        const bool aq = (last ? p.last : p.mid).agg_q16;
         const int nbh = (nodes + kNodesPerBlockH - 1) / kNodesPerBlockH;
         const dim3 grid(nbh < cap ? nbh : cap);
-        if (a.hs_q16) { if (self) launch_half<true, true>(a, grid, s, loop); else launch_half<true, false>(a, grid, s, loop); }
-        else { if (self) launch_half<false, true>(a, grid, s, loop); else launch_half<false, false>(a, grid, s, loop); }
+        if (a.hs_q16) { if (self) launch_half<true, true>(a, aq, grid, s, loop); else launch_half<true, false>(a, aq, grid, s, loop); }
+        else { if (self) launch_half<false, true>(a, aq, grid, s, loop); else launch_half<false, false>(a, aq, grid, s, loop); }
         return;
     }
     const int nb = (nodes + kNodesPerBlock - 1) / kNodesPerBlock;

@@ -231,30 +231,11 @@ struct ag_model {
     size_t dev_floats = 0;
     AgWeights w{};
     // optional profiling (ag_profile_enable): event pairs per kernel class, recorded on the caller's stream
-    int fuse_agg = 0;           // segment reduce inside node_update (env AG_FUSE_AGG / "fuse_aggregate"): 2 = cooperative LDS-staged reduce
-                                // (precision mode 2 only; other modes keep the launch), 0 = separate aggregate launch (default)
-    int precision = AG_PREC_B3; // env AG_PRECISION=f32|bf16x3|fast / ag_set_option("precision", 0|1|2)
-    int eterm_half = 1;         // precision mode 2 ("fast"): 16-bit (q16) Eterm table, fp16 edge stack
-    int max_blocks = 512;       // persistent grid: 2 workgroups per CU
-    int edge_products = 2;      // precision mode 2: 2 = fp16 edge stack (split-fp16 weights x fp16 activations + e5m2 residual bytes: PrecH3),
-                                // 3 = split-bf16 like mode 1 (env AG_EDGE_PRODUCTS / "edge_products")
+    // engine options (kOptions below, their meaning include/adaptigraph_hip.h; max_blocks is set from the device's CU count), cu_split further down;
+    // resolve_path turns them into a call's kernels
+    int split = 0, fuse_agg = 0, precision = 2, max_blocks = 512, edge_products = 2, edge_ws = 1, node_ws = 1, agg_q16 = 1, node_dedup = 1, self_edges = 1,
+        shared_state = 0;
     bool h2_ok = true;          // every edge-stack weight fits fp16 (else mode 2 keeps the split-bf16 edge stack)
-    int agg_q16 = 1;            // precision mode 2: `agg` as q16 rows between the segment reduce and node_update (env AG_AGG_Q16 / "agg_q16"; default 1, r06): one
-                                // more 16-bit rounding per node and round (unsigned, block-scaled), half the bytes of that table; 0 = fp32 rows
-    int node_ws = 1;            // split-bf16 node_update of the rounds before the last on the weight-stationary kernel (default; env AG_NODE_WS /
-                                // "node_stationary" 0 = the streaming kernel); bit-identical
-    int edge_ws = 1;            // fp16 edge stack (PrecH3) on the weight-stationary kernel (default) or, 0, the streaming one (env AG_EDGE_WS / "edge_stationary")
-    int self_edges = 1;         // ag_rollout: leave the self-loops of attribute classes (1, 0) / (0, 1) out of the per-edge pipeline — one table row per class, added by
-                                // the segment reduce at the self-loop's position (AgFwdArgs::self_info; env AG_SELF_EDGES / "self_edges" 0 = every edge through
-                                // the pipeline); bit-identical
-    int shared_state = 0;       // ag_rollout: roll the tool-less base trajectory out once and compute per sample only the rows that can differ from it
-                                // (ag_shared.hip; env AG_SHARED_STATE / "shared_state"); bit-identical; off by default (the headline benchmark is quoted on the
-                                // full per-sample work)
-    int node_dedup = 1;         // encode each distinct node-encoder input row of a sample once (env AG_NODE_DEDUP / "node_dedup"): 0 = never (every node,
-                                // every step), 1 = where it pays (default: >= 32 768 node-rows x steps per call; below that the two extra small launches cost
-                                // more than the shorter kernels save: 0.126 vs 0.115 ms for one 100-particle forward), 2 = always
-    int stagger = 1;            // offset the rollout streams by one encode stage (env AG_STAGGER=0 disables)
-    int split = 0;              // rollout batch parts on separate streams ("rollout_streams" / env AG_SPLIT): 1..4, or 0 = by the workload (rollout_want)
     hipStream_t aux_stream[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_fork = nullptr, ev_join[4] = {nullptr, nullptr, nullptr, nullptr};
     // CU partitioning of the rollout (env AG_CU_SPLIT / "cu_split"): the first `cu_split` CU-mask bits — cu_split / 8 CUs of EVERY
@@ -433,28 +414,45 @@ struct Timed {   // RAII: bracket one kernel launch with an event pair when prof
     ~Timed() { if (stop) (void)hipEventRecord(stop, s); }
 };
 
-void setup_args(ag_model *m, AgFwdArgs &a, int max_blocks, int steps = 1)      // the model's options -> this call's kernel arguments
+// The kernels one call runs (AgPath, ag_common.h): the one place where the model's options and the call's shape become kernel choices.
+// B, N: the batch of the call (ag_rollout's partition check passes the whole batch, the parts their own); steps: model steps per call; shared:
+// the shared-state rollout, which reads the node encoder through its compact rows whatever "node_dedup" says (its carving leaves no overflow
+// possible).  No model: fp32 tables (the workspace queries of any model).
+AgPath resolve_path(const ag_model *m, int B, int N, int n_inst, int steps = 1, bool shared = false)
+{
+    AgPath p{};
+    if (!m) return p;
+    p.b3 = m->precision >= 1;
+    p.q16 = m->precision == 2;
+    if (!p.b3) p.edge = AG_EDGE_F32;
+    else if (!p.q16 || m->edge_products != 2 || !m->h2_ok) p.edge = AG_EDGE_B3;      // (edge-stack weights beyond fp16's range: split-bf16 edge stack)
+    else if (m->edge_ws && n_inst <= 1 && (long long)B * N * 4 < 0x7fffffffLL) p.edge = AG_EDGE_H3_WS;
+    else p.edge = AG_EDGE_H3;
+    const bool fused = m->fuse_agg == 2 && p.q16;      // the fused reduce needs the q16 table: the other modes keep the launch
+    const bool agg_q16 = m->agg_q16 && p.q16;          // the q16 reduce writes `agg` as q16 rows, every split-bf16 node_update reads them
+    p.mid = {p.b3 && m->node_ws && !fused, fused, agg_q16, p.q16};
+    p.last = {false, fused, agg_q16, false};
+    p.agg_launch = !fused;
+    // (below 32 768 node-rows x steps its two extra small launches cost more than the shorter kernels save: 0.126 vs 0.115 ms, 100 particles)
+    p.dedup = shared || (m->node_dedup && (long long)B * (N + AG_DEDUP_REPS) < 0x7fffff00LL &&
+                         (m->node_dedup >= 2 || (long long)B * N * (steps > 0 ? steps : 1) >= 32768));
+    return p;
+}
+
+void setup_args(ag_model *m, AgFwdArgs &a, const AgPath &p, int max_blocks)      // the call's path -> its kernel arguments
 {
     a.edge_counter = m->profiling ? m->edge_counter : nullptr;
-    a.precision = m->precision;
-    a.eterm_half = m->eterm_half;
-    a.fuse_agg = (m->fuse_agg == 2 && !(a.precision == AG_PREC_B3 && a.eterm_half)) ? 0 : m->fuse_agg;   // mode 2 of the option needs the fp16 table
+    a.precision = p.b3 ? AG_PREC_B3 : AG_PREC_F32;
+    a.eterm_half = p.q16;
     a.max_blocks = max_blocks;     // per call, not per model: a model shared by two callers is not mutated
-    a.edge_products = m->h2_ok ? m->edge_products : 3;      // a checkpoint with edge-stack weights beyond fp16's range keeps the split-bf16 edge stack
-    a.edge_ws = m->edge_ws;
-    a.node_ws = m->node_ws;
-    // `agg` as q16 rows (mode 2): the q16 reduce writes them, every split-bf16 node_update reads them, the fused reduce rounds its sums the same way
-    a.agg_q16 = (m->agg_q16 && a.precision == AG_PREC_B3 && a.eterm_half) ? 1 : 0;
-    a.dedup = m->node_dedup && (long long)a.B * (a.N + AG_DEDUP_REPS) < 0x7fffff00LL &&
-              (m->node_dedup >= 2 || (long long)a.B * a.N * (steps > 0 ? steps : 1) >= 32768);
+    a.dedup = p.dedup;
     a.hr_row = nullptr; a.pn_rows = nullptr; a.h_rows = nullptr; a.hr_full = nullptr; a.hs_full = nullptr;
     if (!a.dedup) a.ovf = nullptr;
-    {   // workgroups of the weight-stationary edge encoder (one per CU): a launch that shares the chip with the other rollout streams
-        // takes 1.5x its share of the CUs, capped at all of them (two-stream rollout, C2, r04: 128 CUs -> 127.8 k, 160 -> 133.3 k, 192 -> 134.2 k, 224 -> 132.1 k,
-        // 256 -> 132.0 k graph-steps/s)
-        const int full = m->max_blocks / AG_MLP_WG_PER_CU, share = max_blocks / AG_MLP_WG_PER_CU * 3 / 2;
-        a.ws_blocks = share < full ? (share > 0 ? share : 1) : (full > 0 ? full : 1);
-    }
+    // workgroups of the weight-stationary edge encoder (one per CU): a launch that shares the chip with the other rollout streams takes 1.5x its
+    // share of the CUs, capped at all of them (two-stream rollout, C2, r04: 128 CUs -> 127.8 k, 160 -> 133.3 k, 192 -> 134.2 k, 224 -> 132.1 k,
+    // 256 -> 132.0 k graph-steps/s)
+    const int full = m->max_blocks / AG_MLP_WG_PER_CU, share = max_blocks / AG_MLP_WG_PER_CU * 3 / 2;
+    a.ws_blocks = share < full ? (share > 0 ? share : 1) : (full > 0 ? full : 1);
     a.status = m->status;
 }
 
@@ -474,21 +472,15 @@ void run_node_encode_fallback(ag_model *m, AgFwdArgs &a, hipStream_t s)
     if (a.dedup) ag_launch_node_encode_fallback(m->w, a, s);
 }
 
-// does this call's edge encoder run on the weight-stationary kernel (the condition ag_launch_edge_encode tests, ag_mlp.hip)
-bool edge_ws_path(const AgFwdArgs &a)
-{
-    return a.precision == AG_PREC_B3 && a.eterm_half && a.edge_products == 2 && a.edge_ws && a.n_inst <= 1 && (long long)a.B * a.N * 4 < 0x7fffffffLL;
-}
-
-void run_edge_encode(ag_model *m, AgFwdArgs &a, hipStream_t s)
+void run_edge_encode(ag_model *m, AgFwdArgs &a, const AgPath &path, hipStream_t s)
 {
     // row-tile claim counter of the STREAMING edge encoders; the weight-stationary kernel (default mode) deals its blocks statically: no fill launch
-    const bool ws = edge_ws_path(a);
+    const bool ws = path.edge == AG_EDGE_H3_WS;
     if (a.tile_ctr && !ws) ag_launch_zero_words(a.tile_ctr, 1, s);
-    { Timed t(m, AG_K_EDGE_ENCODE, s); ag_launch_edge_encode(m->w, a, s); if (a.dedup && !ws && !a.remap_done) ag_launch_send_remap(a, s); }      // (ws: mapped by the node-table launch)
+    { Timed t(m, AG_K_EDGE_ENCODE, s); ag_launch_edge_encode(m->w, a, path, s); if (path.dedup && !ws && !a.remap_done) ag_launch_send_remap(a, s); }      // (ws: mapped by the node-table launch)
 }
 
-void run_propagate(ag_model *m, AgFwdArgs &a, hipStream_t s)
+void run_propagate(ag_model *m, AgFwdArgs &a, const AgPath &path, hipStream_t s)
 {
     for (int p = 0; p < a.pstep; ++p) {
         AgFwdArgs r = a;                 // this round's view of the tables
@@ -510,22 +502,67 @@ void run_propagate(ag_model *m, AgFwdArgs &a, hipStream_t s)
         // 0.2452 ms per launch at C2 (-0.8 %: the cache holds a quarter of one pass, and the reduce is not latency-bound enough to care); same bits.
         // (With the non-temporal hints on the table's loads, ag_common.h, the direction no longer matters: never / always / alternating within 0.5 %.)
         r.agg_reverse = (p & 1) == 0 ? 1 : 0;
-        r.hs_q16 = (a.eterm_half && p > 0) ? 1 : 0;                     // rounds after the first gather the q16 rows the previous node_update wrote
-        r.hs_out_q16 = (a.eterm_half && p + 1 < a.pstep) ? 1 : 0;
-        if (!r.fuse_agg) { Timed t(m, AG_K_AGGREGATE, s); ag_launch_aggregate(r, s); }
-        { Timed t(m, AG_K_NODE_UPDATE, s); ag_launch_node_update(m->w, r, p == a.pstep - 1, s); }
+        const int last = p == a.pstep - 1;
+        const AgNodeUpdate &v = last ? path.last : path.mid;
+        r.hs_q16 = (path.q16 && p > 0) ? 1 : 0;                         // rounds after the first gather the q16 rows the previous node_update wrote
+        r.hs_out_q16 = v.hs_q16;
+        r.agg_q16 = v.agg_q16;
+        if (path.agg_launch) { Timed t(m, AG_K_AGGREGATE, s); ag_launch_aggregate(r, path, last, s); }
+        { Timed t(m, AG_K_NODE_UPDATE, s); ag_launch_node_update(m->w, r, path, last, s); }
         std::swap(a.hr, a.hr_out);
         std::swap(a.hs, a.hs_out);
     }
 }
 
-void run_forward(ag_model *m, AgFwdArgs &a, hipStream_t s)
+// ---- engine options: one row each — the name of ag_set_option / ag_get_option, the environment variable ag_model_create reads, the field, and
+// validate (the value to store, or -1: refused).  An environment value is validated exactly as ag_set_option validates it.
+struct Option {
+    const char *name, *env;
+    int ag_model::*field;
+    int (*accept)(const ag_model *m, int v);
+    const char *takes;      // what `accept` takes (error messages)
+};
+int flag(const ag_model *, int v) { return v != 0; }
+const Option kOptions[] = {
+    {"rollout_streams", "AG_SPLIT", &ag_model::split, [](const ag_model *, int v) { return v >= 0 && v <= AG_MAX_PARTS ? v : -1; }, "0 (by the workload) or 1..4"},
+    {"fuse_aggregate", "AG_FUSE_AGG", &ag_model::fuse_agg, [](const ag_model *, int v) { return v == 0 || v == 2 ? v : -1; }, "0 (separate launch) or 2 (reduce inside node_update)"},
+    {"precision", "AG_PRECISION", &ag_model::precision, [](const ag_model *, int v) { return v >= 0 && v <= 2 ? v : -1; }, "0 (f32), 1 (bf16x3) or 2 (fast)"},
+    {"max_blocks", "AG_MAX_BLOCKS", &ag_model::max_blocks, [](const ag_model *, int v) { return v >= 1 ? v : -1; }, "a positive workgroup count"},
+    {"edge_products", "AG_EDGE_PRODUCTS", &ag_model::edge_products, [](const ag_model *, int v) { return v == 2 || v == 3 ? v : -1; }, "2 (fp16 edge stack) or 3 (split-bf16)"},
+    {"edge_stationary", "AG_EDGE_WS", &ag_model::edge_ws, flag, "any integer (0 = off)"},
+    {"node_stationary", "AG_NODE_WS", &ag_model::node_ws, flag, "any integer (0 = off)"},
+    {"agg_q16", "AG_AGG_Q16", &ag_model::agg_q16, flag, "any integer (0 = off)"},
+    {"node_dedup", "AG_NODE_DEDUP", &ag_model::node_dedup, [](const ag_model *, int v) { return v < 0 ? 0 : (v > 2 ? 2 : v); }, "any integer (clamped to 0..2)"},
+    {"self_edges", "AG_SELF_EDGES", &ag_model::self_edges, flag, "any integer (0 = off)"},
+    {"shared_state", "AG_SHARED_STATE", &ag_model::shared_state, flag, "any integer (0 = off)"},
+    {"cu_split", "AG_CU_SPLIT", &ag_model::cu_split, [](const ag_model *m, int v) { return v == 0 || (v >= 8 && v <= m->n_cus - 8 && !(v & 7)) ? v : -1; },
+     "0 (off) or a multiple of 8 in [8, #CUs - 8]"},
+};
+
+const Option *find_option(const char *name)
 {
-    setup_args(m, a, m->max_blocks);
-    run_node_encode(m, a, s);
-    run_node_encode_fallback(m, a, s);
-    run_edge_encode(m, a, s);
-    run_propagate(m, a, s);
+    for (const Option &o : kOptions)
+        if (!strcmp(name, o.name)) return &o;
+    return nullptr;
+}
+
+// ag_model_create: every option's environment variable, if set — an integer, or for AG_PRECISION also f32 / bf16x3 / fast
+int load_env_options(ag_model *m)
+{
+    static const char *const kPrecisionNames[] = {"f32", "bf16x3", "fast"};
+    for (const Option &o : kOptions) {
+        const char *text = getenv(o.env);
+        if (!text) continue;
+        char *end = nullptr;
+        long long v = strtoll(text, &end, 10);
+        bool parsed = *text && !*end && v == (int)v;
+        for (int i = 0; i < 3 && !parsed && o.field == &ag_model::precision; ++i)
+            if (!strcmp(text, kPrecisionNames[i])) { v = i; parsed = true; }
+        const int stored = parsed ? o.accept(m, (int)v) : -1;
+        if (stored < 0) return fail(AG_ERR_CONFIG, "%s=%s: %s takes %s", o.env, text, o.name, o.takes);
+        m->*o.field = stored;
+    }
+    return AG_OK;
 }
 
 }  // namespace
@@ -550,33 +587,18 @@ int ag_model_create(const ag_model_config *cfg, const float *const *weights, ag_
         if (!weights[i]) return fail(AG_ERR_ARG, "ag_model_create: weight %d is null", i);
     ag_model *m = new ag_model();
     m->cfg = *cfg;
-    if (const char *v = getenv("AG_FUSE_AGG")) m->fuse_agg = atoi(v);
-    if (m->fuse_agg != 0 && m->fuse_agg != 2) m->fuse_agg = 0;
-    if (const char *v = getenv("AG_PRECISION")) {
-        const int mode = (!strcmp(v, "f32") || !strcmp(v, "0")) ? 0 : (!strcmp(v, "bf16x3") || !strcmp(v, "1")) ? 1 : 2;
-        m->precision = mode ? AG_PREC_B3 : AG_PREC_F32;
-        m->eterm_half = mode == 2;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) {
+        m->max_blocks = AG_MLP_WG_PER_CU * prop.multiProcessorCount;
+        m->n_cus = prop.multiProcessorCount;
     }
-    if (const char *v = getenv("AG_SPLIT")) m->split = atoi(v);
-    if (const char *v = getenv("AG_EDGE_WS")) m->edge_ws = atoi(v) != 0;
-    if (const char *v = getenv("AG_NODE_WS")) m->node_ws = atoi(v) != 0;
-    if (const char *v = getenv("AG_AGG_Q16")) m->agg_q16 = atoi(v) != 0;
-    if (const char *v = getenv("AG_EDGE_PRODUCTS")) m->edge_products = atoi(v) == 3 ? 3 : 2;
-    if (const char *v = getenv("AG_STAGGER")) m->stagger = atoi(v);
-    if (const char *v = getenv("AG_NODE_DEDUP")) m->node_dedup = atoi(v);
-    if (const char *v = getenv("AG_SELF_EDGES")) m->self_edges = atoi(v) != 0;
-    if (const char *v = getenv("AG_SHARED_STATE")) m->shared_state = atoi(v) != 0;
-    {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) {
-            m->max_blocks = AG_MLP_WG_PER_CU * prop.multiProcessorCount;
-            m->n_cus = prop.multiProcessorCount;
-        }
-        if (const char *v = getenv("AG_CU_SPLIT")) m->cu_split = atoi(v);
-        if (const char *v = getenv("AG_MAX_BLOCKS")) m->max_blocks = atoi(v);
+    int rc = load_env_options(m);      // (after the CU count: "cu_split" is validated against it)
+    if (rc != AG_OK) {
+        delete m;
+        return rc;
     }
-    int rc = pack_and_upload(m, weights);
+    rc = pack_and_upload(m, weights);
     if (rc == AG_OK && (hipMalloc(reinterpret_cast<void **>(&m->status), sizeof(int)) != hipSuccess ||
                         hipMemset(m->status, 0, sizeof(int)) != hipSuccess))
         rc = fail(AG_ERR_HIP, "ag_model_create: status word allocation failed");
@@ -827,51 +849,20 @@ int ag_train_weight_grads_into(int n_layers, const float *const *dz, const int32
 int ag_set_option(ag_model *m, const char *name, int value)
 {
     if (!m || !name) return fail(AG_ERR_ARG, "ag_set_option: null argument");
-    if (!strcmp(name, "rollout_streams")) {
-        if (value < 0 || value > AG_MAX_PARTS) return fail(AG_ERR_ARG, "ag_set_option: rollout_streams takes 0 (by the workload) or 1..%d, not %d", AG_MAX_PARTS, value);
-        m->split = value;
-    }
-    else if (!strcmp(name, "fuse_aggregate")) {
-        if (value != 0 && value != 2) return fail(AG_ERR_ARG, "ag_set_option: fuse_aggregate takes 0 (separate launch) or 2 (reduce inside node_update), not %d", value);
-        m->fuse_agg = value;
-    }
-    else if (!strcmp(name, "precision")) { m->precision = value ? AG_PREC_B3 : AG_PREC_F32; m->eterm_half = value == 2; }
-    else if (!strcmp(name, "max_blocks")) m->max_blocks = value;
-    else if (!strcmp(name, "edge_products")) {
-        if (value != 2 && value != 3) return fail(AG_ERR_ARG, "ag_set_option: edge_products takes 2 (fp16 edge stack, default) or 3 (split-bf16), not %d", value);
-        m->edge_products = value;
-    }
-    else if (!strcmp(name, "edge_stationary")) m->edge_ws = value != 0;
-    else if (!strcmp(name, "node_stationary")) m->node_ws = value != 0;
-    else if (!strcmp(name, "agg_q16")) m->agg_q16 = value != 0;
-    else if (!strcmp(name, "node_dedup")) m->node_dedup = value < 0 ? 0 : (value > 2 ? 2 : value);
-    else if (!strcmp(name, "self_edges")) m->self_edges = value != 0;
-    else if (!strcmp(name, "shared_state")) m->shared_state = value != 0;
-    else if (!strcmp(name, "cu_split")) {
-        if (value != 0 && (value < 8 || value > m->n_cus - 8 || (value & 7)))
-            return fail(AG_ERR_ARG, "ag_set_option: cu_split takes 0 (off) or a multiple of 8 in [8, %d], not %d", m->n_cus - 8, value);
-        m->cu_split = value;
-    }
-    else return fail(AG_ERR_ARG, "ag_set_option: unknown option '%s'", name);
+    const Option *o = find_option(name);
+    if (!o) return fail(AG_ERR_ARG, "ag_set_option: unknown option '%s'", name);
+    const int stored = o->accept(m, value);
+    if (stored < 0) return fail(AG_ERR_ARG, "ag_set_option: %s takes %s, not %d", name, o->takes, value);
+    m->*o->field = stored;
     return AG_OK;
 }
 
 int ag_get_option(const ag_model *m, const char *name, int *value)
 {
     if (!m || !name || !value) return fail(AG_ERR_ARG, "ag_get_option: null argument");
-    if (!strcmp(name, "rollout_streams")) *value = m->split;
-    else if (!strcmp(name, "fuse_aggregate")) *value = m->fuse_agg;
-    else if (!strcmp(name, "precision")) *value = m->precision == AG_PREC_F32 ? 0 : (m->eterm_half ? 2 : 1);
-    else if (!strcmp(name, "max_blocks")) *value = m->max_blocks;
-    else if (!strcmp(name, "edge_products")) *value = m->edge_products;
-    else if (!strcmp(name, "edge_stationary")) *value = m->edge_ws;
-    else if (!strcmp(name, "node_stationary")) *value = m->node_ws;
-    else if (!strcmp(name, "agg_q16")) *value = m->agg_q16;
-    else if (!strcmp(name, "node_dedup")) *value = m->node_dedup;
-    else if (!strcmp(name, "self_edges")) *value = m->self_edges;
-    else if (!strcmp(name, "shared_state")) *value = m->shared_state;
-    else if (!strcmp(name, "cu_split")) *value = m->cu_split;
-    else return fail(AG_ERR_ARG, "ag_get_option: unknown option '%s'", name);
+    const Option *o = find_option(name);
+    if (!o) return fail(AG_ERR_ARG, "ag_get_option: unknown option '%s'", name);
+    *value = m->*o->field;
     return AG_OK;
 }
 
@@ -960,15 +951,13 @@ int ag_build_edges(const float *pos, const uint8_t *mask, const uint8_t *tool_ma
     return AG_OK;
 }
 
-static bool table16(const ag_model *m) { return m && m->precision == AG_PREC_B3 && m->eterm_half; }      // precision mode 2: q16 rows (320 B)
-
 size_t ag_forward_workspace_bytes(int B, int N, int64_t e_cap) { return ag_forward_workspace_bytes_for(nullptr, B, N, e_cap); }
 
 size_t ag_forward_workspace_bytes_for(const ag_model *m, int B, int N, int64_t e_cap)
 {
     AgFwdArgs a{};
     Carver c(nullptr, 0);
-    carve_forward(c, a, B, N, e_cap, table16(m));
+    carve_forward(c, a, B, N, e_cap, resolve_path(m, B, N, 0).q16);
     return align_up(c.off, 256);
 }
 
@@ -989,10 +978,16 @@ int ag_forward(ag_model *m, const float *state, const float *attrs, const float 
     a.pred_pos = pred_pos; a.pred_motion = pred_motion;
     a.B = B; a.N = N; a.n_p = n_p; a.n_inst = n_instance; a.phys_dim = m->cfg.phys_dim; a.e_cap = (int)e_cap;
     a.pstep = m->cfg.pstep; a.clamp = m->cfg.motion_clamp;
+    const AgPath path = resolve_path(m, B, N, n_instance);
     Carver c(workspace, workspace_bytes);
-    carve_forward(c, a, B, N, e_cap, table16(m));
+    carve_forward(c, a, B, N, e_cap, path.q16);
     if (!c.ok()) return fail(AG_ERR_WS, "ag_forward: workspace %zu < %zu bytes", workspace_bytes, c.off);
-    run_forward(m, a, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    setup_args(m, a, path, m->max_blocks);
+    run_node_encode(m, a, s);
+    run_node_encode_fallback(m, a, s);
+    run_edge_encode(m, a, path, s);
+    run_propagate(m, a, path, s);
     AG_HIP(hipGetLastError());
     return AG_OK;
 }
@@ -1071,6 +1066,7 @@ struct SharedLayout {
 static bool shared_applicable(const ag_model *m, const ag_rollout_params *p)
 {
     if (!m || !p || !m->shared_state || p->B < 2 || p->n_steps < 1) return false;
+    if (m->cfg.pstep > 3) return false;      // (ag_launch_shared_compact marks the touched rows plus two hops: exact for up to three propagation rounds)
     if (m->fuse_agg != 0 || m->cu_split != 0) return false;      // (the fused reduce and the CU-partitioned pipeline keep the plain path)
     if ((long long)(p->B + 1) * (p->N + AG_DEDUP_REPS) >= 0x7fffff00LL) return false;
     if (ag_edge_capacity(p->B + 1, p->N, p->topk, p->connect_tools_all, p->max_tools) >= 0x7fffff00LL) return false;
@@ -1131,9 +1127,10 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
                           const float *thr_sq, const int32_t *repeat, float *out_seq, float *state_final, void *workspace, size_t workspace_bytes,
                           hipStream_t s)
 {
+    const AgPath path = resolve_path(m, p->B + 1, p->N, p->n_instance, p->n_steps, true);
     Carver c(workspace, workspace_bytes);
     SharedLayout L;
-    carve_shared(c, m, p, L, table16(m));
+    carve_shared(c, m, p, L, path.q16);
     if (!c.ok()) return fail(AG_ERR_WS, "ag_rollout (shared state): workspace %zu < %zu bytes", workspace_bytes, c.off);
     AgSharedArgs &sh = L.sh;
     AgFwdArgs &f = L.f;
@@ -1153,12 +1150,10 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
     f.row_ptr = e.row_ptr; f.edge_recv = e.edge_recv; f.edge_send = e.edge_send;
     f.pred_pos = L.pred_pos; f.pred_motion = L.pred_motion;
     f.B = B1; f.N = N; f.n_p = n_p; f.n_inst = p->n_instance; f.phys_dim = Pd; f.pstep = m->cfg.pstep; f.clamp = m->cfg.motion_clamp;
-    setup_args(m, f, m->max_blocks, p->n_steps);
-    f.dedup = 1;                        // the propagation rounds read the node encoder through its compact rows whatever "node_dedup" says (carve: no overflow possible)
-    f.ovf = f.tile_ctr + 3;
+    setup_args(m, f, path, m->max_blocks);
     const int self_rows = m->self_edges ? AG_SELF_ROWS : 0;
     if (self_rows) { e.self_attrs = f.attrs; e.self_class_row0 = f.self_class_row0; }
-    if (edge_ws_path(f)) {              // rider: the per-node input rows of the edge features (all B1 N nodes: the compact edges name their endpoints as nodes)
+    if (path.edge == AG_EDGE_H3_WS) {   // rider: the per-node input rows of the edge features (all B1 N nodes: the compact edges name their endpoints as nodes)
         e.tab_state = f.state; e.tab_attrs = f.attrs; e.tab_pinst = f.p_instance; e.tab_out = f.edge_node_tab;
         e.tab_n_inst = f.n_inst; e.tab_n_p = f.n_p; e.tab_status = f.status;
     }
@@ -1178,8 +1173,8 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
         int riders;
         { Timed tm(m, AG_K_EDGES, s); ag_launch_shared_active(sh, s); riders = ag_launch_build_edges(e, s); ag_launch_shared_compact(sh, s); }
         fE.tab_done = (riders & AG_RIDER_TAB) != 0;
-        run_edge_encode(m, fE, s);
-        run_propagate(m, fP, s);
+        run_edge_encode(m, fE, path, s);
+        run_propagate(m, fP, path, s);
         st.step = ai;
         { Timed tm(m, AG_K_ROLLOUT_STEP, s); ag_launch_rollout_step(st, s); }
     }
@@ -1197,6 +1192,7 @@ size_t ag_rollout_workspace_bytes_for(const ag_model *m, const ag_rollout_params
     if (!p) return 0;
     // ag_rollout carves one layout per batch part and the number of parts is a model option ("rollout_streams", 1..4) the
     // caller may change between this query and the call: size for the largest of the four possible carvings, exactly.
+    const bool q16 = resolve_path(m, p->B, p->N, p->n_instance).q16;
     size_t need = 0;
     for (int want = 1; want <= AG_MAX_PARTS; ++want) {
         const int parts = rollout_parts(p->B, want);
@@ -1207,14 +1203,14 @@ size_t ag_rollout_workspace_bytes_for(const ag_model *m, const ag_rollout_params
             float *a, *b, *d;
             int b0, nb;
             part_range(p->B, parts, k, &b0, &nb);
-            carve_rollout(c, p, nb, f, e, &a, &b, &d, AG_NHIS, table16(m));
+            carve_rollout(c, p, nb, f, e, &a, &b, &d, AG_NHIS, q16);
         }
         need = c.off > need ? c.off : need;
     }
     if (shared_applicable(m, p)) {      // (an option the caller may switch off again before the call: the larger of the two layouts)
         Carver c(nullptr, 0);
         SharedLayout L;
-        carve_shared(c, m, p, L, table16(m));
+        carve_shared(c, m, p, L, q16);
         need = c.off > need ? c.off : need;
     }
     return align_up(need, 256);
@@ -1245,10 +1241,11 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
         }
     if (parts > 1 && !m->ev_fork) AG_HIP(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
     Carver c(workspace, workspace_bytes);
-    struct Part { AgFwdArgs f{}; AgEdgeArgs e{}; float *state, *pp, *pm; int b0, B; } part[AG_MAX_PARTS];
+    struct Part { AgFwdArgs f{}; AgEdgeArgs e{}; AgPath path; float *state, *pp, *pm; int b0, B; } part[AG_MAX_PARTS];
     for (int k = 0; k < parts; ++k) {
         part_range(p->B, parts, k, &part[k].b0, &part[k].B);
-        carve_rollout(c, p, part[k].B, part[k].f, part[k].e, &part[k].state, &part[k].pp, &part[k].pm, H, table16(m));
+        part[k].path = resolve_path(m, part[k].B, N, p->n_instance, p->n_steps);
+        carve_rollout(c, p, part[k].B, part[k].f, part[k].e, &part[k].state, &part[k].pp, &part[k].pm, H, part[k].path.q16);
     }
     if (!c.ok()) return fail(AG_ERR_WS, "ag_rollout: workspace %zu < %zu bytes", workspace_bytes, c.off);
     if (parts > 1) {
@@ -1257,9 +1254,9 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
     }
     const size_t plane = (size_t)N * 3;
     const int part_blocks = m->max_blocks / parts > 0 ? m->max_blocks / parts : 1;   // each part's persistent kernels take an equal share
-    // CU-partitioned pipeline (cu_split > 0; needs >= 2 batch parts and the weight-stationary edge encoder, whose grid is one workgroup per CU)
-    const bool partitioned = m->cu_split >= 8 && m->cu_split <= m->n_cus - 8 && parts >= 2 && m->precision == AG_PREC_B3 && m->eterm_half &&
-                             m->edge_products == 2 && m->h2_ok && m->edge_ws && p->n_instance <= 1 && (long long)p->B * N * 4 < 0x7fffffffLL;
+    // CU-partitioned pipeline (cu_split > 0; needs >= 2 batch parts and the weight-stationary edge encoder for the whole batch, whose grid is one
+    // workgroup per CU)
+    const bool partitioned = m->cu_split > 0 && parts >= 2 && resolve_path(m, p->B, N, p->n_instance).edge == AG_EDGE_H3_WS;
     hipStream_t sE = nullptr, sR = nullptr;
     if (partitioned) {
         const int prc = ensure_partition(m);
@@ -1311,13 +1308,13 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
         // encoder stands in front of the rounds that need it — not in front of the other part's edge build.
         auto encode = [&](int k) {       // sR: [edges built] -> ready;  sE: ready -> encoder -> encoded
             if (hipEventRecord(m->ev_ready[k], sR) != hipSuccess || hipStreamWaitEvent(sE, m->ev_ready[k], 0) != hipSuccess) return AG_ERR_HIP;
-            run_edge_encode(m, part[k].f, sE);
+            run_edge_encode(m, part[k].f, part[k].path, sE);
             return hipEventRecord(m->ev_enc[k], sE) == hipSuccess ? AG_OK : AG_ERR_HIP;
         };
         for (int k = 0; k < parts && rc == AG_OK && p->n_steps > 0; ++k) {
             AgFwdArgs &f = part[k].f;
             { Timed tm(m, AG_K_EDGES, sR); ag_launch_build_edges(part[k].e, sR); }
-            setup_args(m, f, AG_MLP_WG_PER_CU * (m->n_cus - m->cu_split), p->n_steps);     // persistent node kernels: the HBM partition's CUs
+            setup_args(m, f, part[k].path, AG_MLP_WG_PER_CU * (m->n_cus - m->cu_split));  // persistent node kernels: the HBM partition's CUs
             f.ws_blocks = m->cu_split;                                                     // edge encoder: one workgroup per CU of the MFMA partition
             run_node_encode(m, f, sR);
             run_node_encode_fallback(m, f, sR);
@@ -1327,7 +1324,7 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
             for (int k = 0; k < parts && rc == AG_OK; ++k) {
                 AgFwdArgs &f = part[k].f;
                 if (hipStreamWaitEvent(sR, m->ev_enc[k], 0) != hipSuccess) { rc = AG_ERR_HIP; break; }
-                run_propagate(m, f, sR);
+                run_propagate(m, f, part[k].path, sR);
                 run[k].st.step = ai;
                 { Timed tm(m, AG_K_ROLLOUT_STEP, sR); ag_launch_rollout_step(run[k].st, sR); }
                 if (ai < p->n_steps) {
@@ -1343,12 +1340,13 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
             hipStream_t s = run[k].s;
             AgFwdArgs &f = part[k].f;
             AgEdgeArgs &e = part[k].e;
+            const AgPath &path = part[k].path;
             if (ai == 1) {
-                setup_args(m, f, part_blocks, p->n_steps);
+                setup_args(m, f, path, part_blocks);
                 // Riders of the edge builder's launches (AgEdgeArgs): the per-node input rows of the weight-stationary edge encoder and, for a
                 // de-duplicated node encoder, the sender column mapped to compact rows — one 15 us launch per model step less.  The map needs
                 // node_row, so the node encoder (which does not read the edges) goes in front of the first step's edge build.
-                if (edge_ws_path(f)) {
+                if (path.edge == AG_EDGE_H3_WS) {
                     e.tab_state = f.state; e.tab_attrs = f.attrs; e.tab_pinst = f.p_instance; e.tab_out = f.edge_node_tab;
                     e.tab_n_inst = f.n_inst; e.tab_n_p = f.n_p; e.tab_status = f.status;
                 }
@@ -1360,8 +1358,8 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
             f.tab_done = (riders & AG_RIDER_TAB) != 0;
             f.remap_done = (riders & AG_RIDER_MAP) != 0;
             run_node_encode_fallback(m, f, s);
-            run_edge_encode(m, f, s);
-            if (ai == 1 && k == 0 && parts > 1 && m->stagger) {
+            run_edge_encode(m, f, path, s);
+            if (ai == 1 && k == 0 && parts > 1) {
                 // phase offset: the other parts start once part 0 has finished its first MFMA-bound encode stage, so
                 // from then on one stream's HBM-bound segment reduce co-runs with another stream's MFMA-bound stage
                 if (hipEventRecord(m->ev_fork, s0) != hipSuccess) { rc = AG_ERR_HIP; break; }
@@ -1369,7 +1367,7 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
                     if (hipStreamWaitEvent(m->aux_stream[kk], m->ev_fork, 0) != hipSuccess) rc = AG_ERR_HIP;
                 if (rc != AG_OK) break;
             }
-            run_propagate(m, part[k].f, s);
+            run_propagate(m, f, path, s);
             run[k].st.step = ai;
             { Timed tm(m, AG_K_ROLLOUT_STEP, s); ag_launch_rollout_step(run[k].st, s); }
         }

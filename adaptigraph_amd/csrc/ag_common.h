@@ -75,15 +75,11 @@ struct AgFwdArgs {
                               // of fp32 rows — the rounds after the first; round 0 gathers the node encoder's fp32 rows
     int precision;     // AG_PREC_F32 (exact fp32 MFMA) or AG_PREC_B3 (hi/lo bf16 split, 3 MFMAs per product)
     int eterm_half;    // 1: the Eterm table is 16-bit block-scaled fixed point in accumulator order (q16, precision mode 2)
-    int fuse_agg;      // 1: node_update does the segment reduce itself (no aggregate launch, no agg table)
     int max_blocks;    // persistent grid size = resident workgroups (2 per CU)
     float *edge_node_tab;  // (rows_pad, 16): per-node inputs of the edge features [attr0, attr1, group0, 0, v0(3), v1(3), v2(3), x_cur(3)] (weight-stationary edge encoder)
     int *tile_ctr;     // zeroed int: row-tile claim counter of this forward's edge_encode launch (NULL: static grid stride)
     int *status;       // sticky device word of the model: bit 0 = a forward left the range of its arithmetic (ag_model_status)
-    int edge_products; // precision mode 2 only: 2 = fp16 edge stack with residual bytes (PrecH3, default), 3 = split-bf16 like mode 1
     int ws_blocks;     // workgroups of the weight-stationary edge encoder for this launch
-    int edge_ws;       // with edge_products == 2: 1 = weight-stationary kernel (default), 0 = streaming kernel
-    int node_ws;       // split-bf16 node_update of the rounds before the last on the weight-stationary kernel (ag_mlp.hip: node_update_nws_kernel)
     int agg_q16;       // precision mode 2, option "agg_q16" (default 1): the segment reduce stores `agg` as q16 rows (320 B, the Eterm row layout with unsigned
                        // values, ag_q16_encode_segment) and node_update decodes them; the reduce fused into node_update rounds its sums the same way
     // ---- node-encoder de-duplication.  The node encoder sees [attrs | phys | action] only (positions do not enter:
@@ -359,13 +355,27 @@ __device__ __forceinline__ void ag_reduce_node_q16(const AgFwdArgs &a, int g, in
     if (a.status && !isfinite(((acc0.x + acc0.y) + (acc0.z + acc0.w)) + ((acc1.x + acc1.y) + (acc1.z + acc1.w)))) atomicOr(a.status, 1);
 }
 
+// The kernels one forward runs, decided once per call from the model's options and the call's shape (ag_api.hip: resolve_path); the
+// launchers and the sequencer dispatch on it and re-derive nothing.  Edge encoder: fp32 MFMA (precision 0), split-bf16, or the fp16 edge stack with
+// residual bytes (precision 2, "edge_products" 2) on the streaming or the weight-stationary kernel.
+enum AgEdgeEncoder { AG_EDGE_F32, AG_EDGE_B3, AG_EDGE_H3, AG_EDGE_H3_WS };
+struct AgNodeUpdate { bool ws, fused, agg_q16, hs_q16; };   // one kind of round: weight-stationary kernel, reduce inside, `agg` in / Hs out as q16 rows
+struct AgPath {
+    bool b3;                  // split-bf16 node stacks (precision 1 and 2), else fp32
+    bool q16;                 // per-edge table and the sender rows of the rounds after the first as q16 rows (precision 2), else fp32 rows
+    AgEdgeEncoder edge;
+    AgNodeUpdate mid, last;   // the rounds before the last / the last round
+    bool agg_launch;          // the segment reduce is a launch of its own
+    bool dedup;               // node-encoder de-duplication (AgFwdArgs::dedup)
+};
+
 // kernel launchers (one translation unit each)
 void ag_launch_node_encode(const AgWeights &w, const AgFwdArgs &a, hipStream_t s);
 void ag_launch_node_encode_fallback(const AgWeights &w, const AgFwdArgs &a, hipStream_t s);
 void ag_launch_send_remap(const AgFwdArgs &a, hipStream_t s);
-void ag_launch_edge_encode(const AgWeights &w, const AgFwdArgs &a, hipStream_t s);
-void ag_launch_aggregate(const AgFwdArgs &a, hipStream_t s);
-void ag_launch_node_update(const AgWeights &w, const AgFwdArgs &a, int last, hipStream_t s);
+void ag_launch_edge_encode(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, hipStream_t s);
+void ag_launch_aggregate(const AgFwdArgs &a, const AgPath &p, int last, hipStream_t s);
+void ag_launch_node_update(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, int last, hipStream_t s);
 
 struct AgEdgeArgs {
     const float *pos;            // (B, N, 3) with pos_stride floats between samples

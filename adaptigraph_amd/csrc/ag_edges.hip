@@ -16,7 +16,6 @@
 //           batch_mask and the tool->tool edges it keeps (graph.py:77-80 vs :134-144)
 //   order : (receiver, sender) ascending == adj_matrix.nonzero() row-major order (graph.py:151)
 #include "ag_common.h"
-#include <cstdlib>
 
 namespace {
 
@@ -880,18 +879,16 @@ int ag_launch_build_edges(const AgEdgeArgs &a, hipStream_t s)
     const int rows = a.B * a.N;
     int riders = 0;
     // (connect_tools_all: the per-sample batch_mask word is cleared by bin_kernel on the cell path — one fill launch per step less)
-    static const int force = getenv("AG_EDGE_CELLS") ? atoi(getenv("AG_EDGE_CELLS")) : -1;   // -1 auto, 0 brute force, 1 cells
-    const bool cells = force < 0 ? a.N >= 256 : force != 0;
+    const bool cells = a.N >= 256;      // cell binning, else the brute-force scan
     if (a.connect && !cells) ag_launch_zero_words(a.flag, a.B, s);
     if (cells) {
         const int nb_tab = a.tab_out ? (rows + 255) / 256 : 0;        // rider workgroups follow the B binning ones
         hipLaunchKernelGGL(bin_kernel, dim3(a.B + nb_tab), dim3(256), 0, s, a);
         if (nb_tab) riders |= AG_RIDER_TAB;
         const dim3 lgrid((a.N + 255) / 256, a.B);
-        static const int packed = getenv("AG_EDGE_PACKED") ? atoi(getenv("AG_EDGE_PACKED")) : 1;      // 0: the exact (d, j) network for every receiver
         int jb = 1;
         while ((1 << jb) < a.N) ++jb;
-        const bool pk = packed && jb <= 16;          // >= 16 bits of d in the key (else nearly every boundary would be ambiguous)
+        const bool pk = jb <= 16;                    // packed (d, j) keys need >= 16 bits of d (else nearly every boundary would be ambiguous)
         if (a.cap0 == 5 && a.topk == 5) {
             if (pk) hipLaunchKernelGGL(select_lanes_packed_kernel<5>, lgrid, dim3(256), 0, s, a, jb);
             else hipLaunchKernelGGL(select_lanes_kernel<5>, lgrid, dim3(256), 0, s, a);

@@ -2275,11 +2275,8 @@ void ag_launch_node_encode(const AgWeights &w, const AgFwdArgs &a, hipStream_t s
         else hipLaunchKernelGGL((node_encode_kernel<PrecF32, true>), gridc, blockc, 0, s, w, a);
         return;
     }
-    const dim3 grid(grid_for(a.B * a.N, a.max_blocks)), block(AG_MLP_THREADS);
-    if (a.precision == AG_PREC_B3) hipLaunchKernelGGL((node_encode_kernel<PrecB3, false>), grid, block, 0, s, w, a);
-    else hipLaunchKernelGGL((node_encode_kernel<PrecF32, false>), grid, block, 0, s, w, a);
+    ag_launch_node_encode_fallback(w, a, s);      // (the per-node encoder)
 }
-
 
 void ag_launch_node_encode_fallback(const AgWeights &w, const AgFwdArgs &a, hipStream_t s)
 {
@@ -2288,56 +2285,52 @@ void ag_launch_node_encode_fallback(const AgWeights &w, const AgFwdArgs &a, hipS
     else hipLaunchKernelGGL((node_encode_kernel<PrecF32, false>), grid, block, 0, s, w, a);
 }
 
-void ag_launch_edge_encode(const AgWeights &w, const AgFwdArgs &a, hipStream_t s)
+void ag_launch_edge_encode(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, hipStream_t s)
 {
     if (a.e_cap <= 0) return;
     const dim3 block(AG_MLP_THREADS);
     const int e_max = a.e_cap + a.self_rows;      // upper bound of the rows this launch encodes (the true count is on the device)
-    if (a.precision == AG_PREC_B3 && a.eterm_half && a.edge_products == 2) {     // mode 2: two fp16 products per k16-step, three workgroups per CU
-        if (a.edge_ws && a.n_inst <= 1 && (long long)a.B * a.N * 4 < 0x7fffffffLL) {        // weight-stationary: one workgroup per CU, 32-edge blocks
-            const int blocks = (e_max + 31) / 32, slots = a.ws_blocks;
-            const int nb_tab = a.tab_done ? 0 : (a.B * a.N + 255) / 256;
-            const int nb_map = a.dedup && !a.remap_done ? ((a.e_cap + 1023) / 1024 < 4096 ? (a.e_cap + 1023) / 1024 : 4096) : 0;      // four edges per thread
-            if (nb_tab + nb_map > 0) hipLaunchKernelGGL(edge_node_tab_kernel, dim3(nb_tab + nb_map), dim3(256), 0, s, a, nb_tab);
-            hipLaunchKernelGGL(edge_encode_ws_kernel, dim3(blocks < slots ? blocks : (slots > 0 ? slots : 1)), dim3(512), 0, s, w, a);   // (always eight waves, whatever AG_MLP_THREADS is)
-            return;
-        }
-        const dim3 grid(grid_for(e_max, a.max_blocks / AG_MLP_WG_PER_CU * AG_H3_WG_PER_CU));
-        hipLaunchKernelGGL(edge_encode_kernel<PrecH3>, grid, block, 0, s, w, a);
+    switch (p.edge) {
+    case AG_EDGE_H3_WS: {      // weight-stationary: one workgroup per CU, 32-edge blocks
+        const int blocks = (e_max + 31) / 32, slots = a.ws_blocks;
+        const int nb_tab = a.tab_done ? 0 : (a.B * a.N + 255) / 256;
+        const int nb_map = p.dedup && !a.remap_done ? ((a.e_cap + 1023) / 1024 < 4096 ? (a.e_cap + 1023) / 1024 : 4096) : 0;      // four edges per thread
+        if (nb_tab + nb_map > 0) hipLaunchKernelGGL(edge_node_tab_kernel, dim3(nb_tab + nb_map), dim3(256), 0, s, a, nb_tab);
+        hipLaunchKernelGGL(edge_encode_ws_kernel, dim3(blocks < slots ? blocks : (slots > 0 ? slots : 1)), dim3(512), 0, s, w, a);   // (always eight waves, whatever AG_MLP_THREADS is)
         return;
     }
-    const dim3 grid(grid_for(e_max, a.max_blocks));
-    if (a.precision == AG_PREC_B3) hipLaunchKernelGGL(edge_encode_kernel<PrecB3>, grid, block, 0, s, w, a);
-    else hipLaunchKernelGGL(edge_encode_kernel<PrecF32>, grid, block, 0, s, w, a);
+    case AG_EDGE_H3: hipLaunchKernelGGL(edge_encode_kernel<PrecH3>, dim3(grid_for(e_max, a.max_blocks / AG_MLP_WG_PER_CU * AG_H3_WG_PER_CU)), block, 0, s, w, a); return;
+    case AG_EDGE_B3: hipLaunchKernelGGL(edge_encode_kernel<PrecB3>, dim3(grid_for(e_max, a.max_blocks)), block, 0, s, w, a); return;
+    case AG_EDGE_F32: hipLaunchKernelGGL(edge_encode_kernel<PrecF32>, dim3(grid_for(e_max, a.max_blocks)), block, 0, s, w, a); return;
+    }
 }
 
-void ag_launch_node_update(const AgWeights &w, const AgFwdArgs &a, int last, hipStream_t s)
+void ag_launch_node_update(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, int last, hipStream_t s)
 {
+    const AgNodeUpdate &v = last ? p.last : p.mid;
     const dim3 grid(grid_for(a.B * a.N, a.max_blocks)), block(AG_MLP_THREADS);
-    if (a.precision == AG_PREC_B3 && !last && a.node_ws && !a.fuse_agg) {      // weight-stationary kernel: one workgroup per CU
+    if (v.ws) {      // weight-stationary kernel: one workgroup per CU
         const int cus = a.max_blocks / AG_MLP_WG_PER_CU > 0 ? a.max_blocks / AG_MLP_WG_PER_CU : 1, nblk = (a.B * a.N + 31) / 32;
         const dim3 g2(nblk < cus ? nblk : cus);
         // (agg_q16 is a mode-2 option and mode 2 writes the next round's sender table as q16 rows: the combination <false, true> does not exist)
-        if (a.agg_q16 && a.hs_out_q16) hipLaunchKernelGGL((node_update_nws_kernel<true, true>), g2, dim3(256), 0, s, w, a);
-        else if (a.hs_out_q16) hipLaunchKernelGGL((node_update_nws_kernel<true, false>), g2, dim3(256), 0, s, w, a);
+        if (v.agg_q16 && v.hs_q16) hipLaunchKernelGGL((node_update_nws_kernel<true, true>), g2, dim3(256), 0, s, w, a);
+        else if (v.hs_q16) hipLaunchKernelGGL((node_update_nws_kernel<true, false>), g2, dim3(256), 0, s, w, a);
         else hipLaunchKernelGGL((node_update_nws_kernel<false, false>), g2, dim3(256), 0, s, w, a);
         return;
     }
-    if (a.precision == AG_PREC_B3) {
-        if (a.fuse_agg == 2 && a.eterm_half) {      // cooperative LDS-staged reduce inside the kernel (no aggregate launch, no agg table)
-            if (last) hipLaunchKernelGGL((node_update_kernel<PrecB3, true, true>), grid, block, 0, s, w, a);
-            else if (a.hs_out_q16) hipLaunchKernelGGL((node_update_kernel<PrecB3, false, true, true>), grid, block, 0, s, w, a);
-            else hipLaunchKernelGGL((node_update_kernel<PrecB3, false, true>), grid, block, 0, s, w, a);
-        } else if (a.agg_q16 && (last || a.hs_out_q16)) {      // (mode 2 only: `agg` arrives as q16 rows; its rounds before the last write Hs as q16 rows)
-            if (last) hipLaunchKernelGGL((node_update_kernel<PrecB3, true, false, false, true>), grid, block, 0, s, w, a);
-            else hipLaunchKernelGGL((node_update_kernel<PrecB3, false, false, true, true>), grid, block, 0, s, w, a);
-        } else if (last) hipLaunchKernelGGL((node_update_kernel<PrecB3, true, false>), grid, block, 0, s, w, a);
-        else if (a.hs_out_q16) hipLaunchKernelGGL((node_update_kernel<PrecB3, false, false, true>), grid, block, 0, s, w, a);
-        else hipLaunchKernelGGL((node_update_kernel<PrecB3, false, false>), grid, block, 0, s, w, a);
-    } else {
+    if (!p.b3) {
         if (last) hipLaunchKernelGGL((node_update_kernel<PrecF32, true, false>), grid, block, 0, s, w, a);
         else hipLaunchKernelGGL((node_update_kernel<PrecF32, false, false>), grid, block, 0, s, w, a);
-    }
+    } else if (v.fused) {      // cooperative LDS-staged reduce inside the kernel (no aggregate launch, no agg table)
+        if (last) hipLaunchKernelGGL((node_update_kernel<PrecB3, true, true>), grid, block, 0, s, w, a);
+        else if (v.hs_q16) hipLaunchKernelGGL((node_update_kernel<PrecB3, false, true, true>), grid, block, 0, s, w, a);
+        else hipLaunchKernelGGL((node_update_kernel<PrecB3, false, true>), grid, block, 0, s, w, a);
+    } else if (v.agg_q16) {    // (mode 2 only: `agg` arrives as q16 rows; its rounds before the last write Hs as q16 rows)
+        if (last) hipLaunchKernelGGL((node_update_kernel<PrecB3, true, false, false, true>), grid, block, 0, s, w, a);
+        else hipLaunchKernelGGL((node_update_kernel<PrecB3, false, false, true, true>), grid, block, 0, s, w, a);
+    } else if (last) hipLaunchKernelGGL((node_update_kernel<PrecB3, true, false>), grid, block, 0, s, w, a);
+    else if (v.hs_q16) hipLaunchKernelGGL((node_update_kernel<PrecB3, false, false, true>), grid, block, 0, s, w, a);
+    else hipLaunchKernelGGL((node_update_kernel<PrecB3, false, false>), grid, block, 0, s, w, a);
 }
 
 void ag_launch_train_pack(const float *W, const float *bias, int n_out, int n_in, int ld, int col0, int transposed, int compact,

@@ -133,14 +133,8 @@ class DynamicsPredictor(nn.Module):
         return flags.value
 
     def set_option(self, name, value, device=None):
-        """Engine knob (include/adaptigraph_hip.h: ag_set_option): "precision" 0 = exact fp32 MFMA, 1 = split-bf16 with an
-        fp32 per-edge table, 2 = split-bf16 node stacks + fp16 edge stack with residual bytes + 16-bit block-scaled per-edge
-        table ("fast", the default; its fp16 activations have fp16's range, see take_status); "rollout_streams"; "node_dedup";
-        "fuse_aggregate"; "max_blocks"; "edge_products"; "edge_stationary"; "node_stationary"; "cu_split"; "self_edges" (r06: self-loops of the
-        attribute classes (1, 0) / (0, 1) as one table row per class, default 1); "shared_state" (r06: rollouts of one cloud under many sampled
-        pushes compute per sample only what can differ from the tool-less base trajectory, default 0).  All of them give the same bits, except
-        "precision" and "agg_q16" (r06, default 0: the per-node sums of a round travel as 16-bit block-scaled rows between the segment reduce and
-        node_update in mode 2 — one more rounding per node and round)."""
+        """Engine knob: ag_set_option.  The option list, with each option's values, default and environment variable, is in
+        include/adaptigraph_hip.h."""
         dev = torch.device(device if device is not None else self.device)
         _lib.check(_lib.lib().ag_set_option(self.handle(dev), name.encode(), int(value)), f"ag_set_option({name})")
         return self

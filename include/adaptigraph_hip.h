@@ -57,12 +57,17 @@ int ag_model_create(const ag_model_config *cfg, const float *const *weights, ag_
 int ag_model_update_weights(ag_model *m, const float *const *weights);
 int ag_model_destroy(ag_model *m);
 
-/* Engine knobs (all have sane defaults; used by bench.py for A/B passes):
+/* Engine knobs (all have sane defaults; used by bench.py for A/B passes).  ag_model_create also reads each from an environment variable, an integer
+ * validated as here (AG_PRECISION also takes f32 / bf16x3 / fast); an invalid value makes it return AG_ERR_CONFIG:
+ *   AG_SPLIT rollout_streams, AG_FUSE_AGG fuse_aggregate, AG_MAX_BLOCKS max_blocks, AG_EDGE_PRODUCTS edge_products, AG_EDGE_WS edge_stationary,
+ *   AG_NODE_WS node_stationary, AG_NODE_DEDUP node_dedup, AG_SELF_EDGES self_edges, AG_SHARED_STATE shared_state, AG_AGG_Q16 agg_q16,
+ *   AG_CU_SPLIT cu_split, AG_PRECISION precision.
+ * Values outside an option's list are refused (AG_ERR_ARG), except that the 0/1 switches take any integer (non-zero = 1) and "node_dedup" clamps to 0..2.
  *   "rollout_streams"  0..4  ag_rollout runs the batch as this many independent parts on separate streams; 0 (default): the engine's choice by
  *                            workload, see ag_rollout_streams_for
  *   "fuse_aggregate"   0/2   segment reduce as its own HBM-streaming kernel (0, default) or inside node_update through an LDS stage
- *                            (2, precision 2 only: no `agg` table; measured equal solo, -4 % in the two-stream rollout); bit-identical results
- *   "max_blocks"       n     persistent grid size (default 2 x #CUs)
+ *                            (2, precision 2 only, other modes keep the launch: no `agg` table; measured equal solo, -4 % in the two-stream rollout); bit-identical results
+ *   "max_blocks"       n >= 1 persistent grid size (default 2 x #CUs)
  *   "edge_products"    2/3   precision 2 only: arithmetic of the EDGE stack: 2 = fp16 (default: split-fp16 weights x fp16 activations + an e5m2
  *                            residual byte per activation, three fp16 MFMAs per fp32 product; models whose edge weights exceed the fp16 range
  *                            keep 3), 3 = split-bf16 like precision 1
@@ -86,14 +91,15 @@ int ag_model_destroy(ag_model *m);
  *                            sample 0 with its tool slots invalid) is rolled out once as an extra internal sample; per model step every sample's full edge
  *                            lists are still built, but the encoders and the propagation rounds run only over the rows whose result can differ from the
  *                            base's — nodes whose inputs or earlier predictions differ in any bit (tool slots always), rows whose edge list differs from
- *                            the base's, and their 3-hop closure (three propagation rounds) — and every other particle takes the base's prediction.
+ *                            the base's, and their 3-hop closure (three propagation rounds) — and every other particle takes the base's prediction
+ *                            (models with more than three rounds, pstep > 3, take the plain path).
  *                            Results equal the plain rollout bit for bit for ANY input (samples whose states differ from sample 0's are simply all
  *                            private); one stream, node de-duplication forced on, workspace of ag_rollout_workspace_bytes_for(model, ...) with the option
  *                            set.  0 (default) = every sample in full — what the headline benchmark is quoted on.  Not combined with
  *                            "fuse_aggregate" 2 / "cu_split" (those calls take the plain path)
  *   "agg_q16"          0/1   precision 2 with the defaults of "fuse_aggregate" / "node_stationary": 1 = the per-node sums of a propagation round (`agg`,
  *                            model.py:295) travel from the segment reduce to node_update as 16-bit block-scaled rows (the per-edge table's format, 320 B
- *                            instead of 640 B per node and round).  One more rounding per node and round: NOT bit-identical to 0 (default) — measured
+ *                            instead of 640 B per node and round; default 1).  One more rounding per node and round: NOT bit-identical to 0 — measured
  *                            deviation and gain in docs/NEGATIVE_RESULTS.md R6.4; ignored where a kernel of the round does not read the format
  *   "cu_split"         0|8k  CU-partitioned rollout (off by default): the first `cu_split` CU-mask bits (cu_split / 8 CUs of every XCD) run the
  *                            MFMA-bound edge encoder, the other CUs the HBM-bound edge build / segment reduce / node update / state step, the batch

@@ -37,17 +37,22 @@ def test_dynamic_symbol_table_is_exactly_the_header():
     assert exported == declared_symbols()
 
 
-def test_every_engine_option_is_documented_in_the_header_and_readable():
-    """The option names ag_set_option accepts (csrc/ag_api.hip) are exactly the ones ag_get_option answers, and each is described in the header's option list
-    (a caller of the C ABI has nothing else to go by)."""
+def test_every_engine_option_is_one_table_row_documented_in_the_header():
+    """ag_set_option, ag_get_option and ag_model_create's environment all go through one option table (csrc/ag_api.hip: kOptions), one row per
+    option (name, environment variable, field, validation), so the names set and get accept are the same by construction; each option and its
+    environment variable is described in the header's option list (a caller of the C ABI has nothing else to go by)."""
     src = open(os.path.join(ROOT, "adaptigraph_amd", "csrc", "ag_api.hip")).read()
-    body = lambda fn: src[src.index(f"int {fn}("):src.index("return AG_OK;", src.index(f"int {fn}("))]
-    names = lambda fn: set(re.findall(r'!strcmp\(name, "([a-z0-9_]+)"\)', body(fn)))
-    setters, getters = names("ag_set_option"), names("ag_get_option")
-    assert setters == getters and len(setters) >= 12
+    table = src[src.index("const Option kOptions[] = {"):src.index("};", src.index("const Option kOptions[] = {"))]
+    rows = re.findall(r'\{"([a-z0-9_]+)", "(AG_[A-Z0-9_]+)", &ag_model::[a-z0-9_]+, ', table)
+    names, envs = [r[0] for r in rows], [r[1] for r in rows]
+    assert len(rows) == table.count('{"') and len(set(names)) == len(names) >= 12 and len(set(envs)) == len(envs)
+    for fn in ("ag_set_option", "ag_get_option"):
+        body = src[src.index(f"int {fn}("):src.index("return AG_OK;", src.index(f"int {fn}("))]
+        assert "find_option(name)" in body and "strcmp" not in body, fn
     header = open(os.path.join(ROOT, "include", "adaptigraph_hip.h")).read()
-    for n in sorted(setters):
+    for n, e in rows:
         assert f'"{n}"' in header, f"option {n} is not described in include/adaptigraph_hip.h"
+        assert e in header, f"environment variable {e} of option {n} is not named in include/adaptigraph_hip.h"
 
 
 def test_version_and_capacity_queries():

@@ -618,6 +618,30 @@ def test_shared_state_rollout_is_bitwise_the_plain_rollout(weights, mode, materi
     assert m.take_status() == 0
 
 
+def test_shared_state_rollout_of_a_four_round_model_is_bitwise_the_plain_rollout(weights):
+    """The shared-state rollout marks the rows a tool touches plus two hops (ag_shared.hip): the light cone of three propagation rounds.  A model with
+    pstep = 4 reaches one hop further, so with "shared_state" 1 it must take the plain path.  A 300-particle rope pushed at one end has particles four
+    and more hops from the tool: same bits as the plain rollout."""
+    cfg = configs.model_config()
+    cfg["pstep"] = 4
+    m = DynamicsPredictor(cfg, configs.material_config("rope"), configs.dataset_config("rope"), DEV)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in weights.items()})
+    m = m.to(DEV).eval()
+    rng = np.random.default_rng(4)
+    state, act = synth.make_mpc_inputs("rope", 300, 16, seed=4, len_lo=3, len_hi=3.9, spacing=0.1)
+    act[..., 0] = rng.uniform(0.0, 0.4, act.shape[:2])            # the pusher starts at the rope's end (x = 0, z = 0) ...
+    act[..., 1] = rng.uniform(-0.3, 0.3, act.shape[:2])           # ... and the far end is 30 units away
+
+    def run():
+        return dynamics(t(state), t(act), m, DEV, _ppm("rope"))["state_seqs"].clone()
+
+    ref = run()
+    assert torch.isfinite(ref).all() and not torch.equal(ref[0], ref[1])
+    m.set_option("shared_state", 1)
+    assert torch.equal(ref, run())
+    assert m.take_status() == 0
+
+
 def test_shared_state_rollout_with_distinct_states_degrades_to_the_plain_rollout(weights):
     """Per-sample DISTINCT states (dynamics_masked: every sample its own cloud and mask; and ag_rollout with perturbed per-sample inputs): nothing can be
     shared — every node is dirty from the first step on and the option reduces to the plain rollout plus one base sample.  Same bits.  Partially
@@ -1093,6 +1117,11 @@ def test_cu_partitioned_rollout_is_bitwise_the_shared_chip_rollout(weights, spli
     assert torch.equal(dynamics(t(state), t(act), m, DEV, _ppm("rope"))["state_seqs"], ref) and m.take_status() == 0
     with pytest.raises(RuntimeError):
         m.set_option("cu_split", 100)           # not a multiple of 8
+    for name, bad in (("precision", 3), ("max_blocks", 0)):
+        before = m.get_option(name)
+        with pytest.raises(RuntimeError):
+            m.set_option(name, bad)
+        assert m.get_option(name) == before, name
 
 
 def test_get_option_reports_what_the_engine_runs_with(weights):
