@@ -99,7 +99,7 @@ float bf16_to_f32(uint16_t b)
 //   F32: [5 tiles][32 rows][32 floats], 16-byte XOR swizzle;  B3: [5 tiles][NU steps][hi|lo][64 lanes][8 bf16]
 // b3: 0 = fp32 image, 1 = split-bf16 fragment image, 2 = split-fp16 fragment image (same layout)
 // lo_feat0 >= 0 (split-fp16 edge stack): image columns K + 1 + i repeat input column lo_feat0 + i, i < K - lo_feat0 — the kernels put the
-// fp16 rounding residual of that input there (ag_mlp.hip, f16_residual), so the first layer multiplies hi + lo of those inputs.
+// fp16 rounding residual of that input there (ag_mlp_dev.h, f16_residual), so the first layer multiplies hi + lo of those inputs.
 void pack_first_layer(std::vector<float> &dst, int b3, const float *W, int K, int n_out, const float *bias, int lo_feat0 = -1)
 {
     const size_t base = dst.size();
@@ -161,7 +161,7 @@ void pack_layer(std::vector<float> &dst, int b3, const float *W, int ld, int col
     }
 }
 
-// One wide layer of the fp16 edge stack (PrecH3, ag_mlp.hip) as n_tiles chunk images of 20 480 bytes + their block scales:
+// One wide layer of the fp16 edge stack (PrecH3, ag_mlp_dev.h) as n_tiles chunk images of 20 480 bytes + their block scales:
 //   bytes [0, 10240):      hi = fp16(W) fragments, [10 k16-steps u][64 lanes (i, h)][8 fp16], slot e = column 16u + 8(e>>2) + 4h + (e&3)
 //   bytes [10240, 20480):  the A operands of the block-scaled fp8 MFMA (v_mfma_scale_f32_32x32x64_f8f6f4), [5 input tiles t][64 lanes (i, h)][32 B]:
 //                          bytes 0..15 = e4m3(W_lo / s_lo), bytes 16..31 = e4m3(W_hi / s_hi) of columns 32t + 8q + 4h + p at byte 4q + p

@@ -153,7 +153,7 @@ __device__ __forceinline__ int ag_q16_exp_byte_offset(int t, int h) { return h ?
 __device__ __forceinline__ float ag_q16_scale(int eb) { return ldexpf(1.0f / 32767.0f, eb - 126); }
 
 // ---- segment reduce of ONE node over the q16 table, shared by aggregate_half_kernel (ag_aggregate.hip) and the reduce fused into
-//      node_update (ag_mlp.hip) ------------------------------------------------------------------------------------------------------
+//      node_update (ag_node_update.hip) ------------------------------------------------------------------------------------------------------
 // Twenty adjacent lanes of ONE wave own a node (three nodes per wave, lanes 60..63 idle); lane c (0..19) owns the 16-byte segment c of
 // every edge row = features f0 + {0..3} and f0 + 8 + {0..3}, f0 = ag_half_lane_feature(c), of out-tile c >> 2.  The tile's exponent byte
 // arrives by ONE ds_bpermute per edge from the third dword of lane 17's (tiles 0..3) or lane 19's (tile 4) own load — no extra memory
@@ -201,7 +201,7 @@ __device__ __forceinline__ void ag_st_nt(int4 *p, const int4 &v) { __builtin_non
 // tile maximum is two quad-permute DPP moves away; the five exponent bytes reach the two lanes whose segments hold them (17: bytes 280..284, 19:
 // bytes 312, 316..319 — the Eterm row format above, byte for byte) by four ds_bpermute.  Values are sums of ReLU outputs (>= +0), padding positions are
 // already zero (ag_reduce_node_q16's tail).  Because nothing is negative the 16 bits are UNSIGNED here — q = rne(v 2^(126-eb) 65535), value = q 2^(eb-126) / 65535:
-// half the rounding step of the signed per-edge rows (the one difference to that format; only node_update reads these rows, ag_mlp.hip: agg_q16_*).
+// half the rounding step of the signed per-edge rows (the one difference to that format; only node_update reads these rows, ag_mlp_dev.h: agg_q16_*).
 __device__ __forceinline__ float ag_q16u_scale(int eb) { return ldexpf(1.0f / 65535.0f, eb - 126); }
 // the eight values of a lane as 16-bit words (no exponent bytes yet) + the tile's exponent byte
 __device__ __forceinline__ int4 ag_q16_quantize_segment(const float4 &acc0, const float4 &acc1, int &eb)
@@ -376,6 +376,9 @@ void ag_launch_send_remap(const AgFwdArgs &a, hipStream_t s);
 void ag_launch_edge_encode(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, hipStream_t s);
 void ag_launch_aggregate(const AgFwdArgs &a, const AgPath &p, int last, hipStream_t s);
 void ag_launch_node_update(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, int last, hipStream_t s);
+// the weight-stationary arms of the two switches over AgPath above (ag_edge_encode.hip, ag_node_update.hip): their kernels are a unit of their own
+void ag_launch_edge_encode_ws(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, hipStream_t s);
+void ag_launch_node_update_ws(const AgWeights &w, const AgFwdArgs &a, const AgNodeUpdate &v, hipStream_t s);
 
 struct AgEdgeArgs {
     const float *pos;            // (B, N, 3) with pos_stride floats between samples
@@ -424,7 +427,7 @@ int ag_launch_build_edges(const AgEdgeArgs &a, hipStream_t s);      // returns t
 // Per-node inputs of the edge features (model.py:155-165, 220-253), 64 bytes per node, so that the weight-stationary edge encoder's gather is
 // two indexed 64-byte rows per edge: [attr0, attr1, group0, 0 | v0 | v1 | v2 | x_cur], v_i = state[i+1] - state[i].  The per-edge features are
 // then plain differences of two rows — the same subtractions in the same order as (pr[i+1] - pr[i]) - (ps[i+1] - ps[i]) in edge_features.
-// One thread per node g; shared by edge_node_tab_kernel (ag_mlp.hip) and the rider workgroups of bin_kernel (ag_edges.hip).
+// One thread per node g; shared by edge_node_tab_kernel (ag_edge_encode_ws.hip) and the rider workgroups of bin_kernel (ag_edges.hip).
 // `class_row0` >= 0 (self-edge elision): rows class_row0 + k, k < AG_SELF_ROWS, are the two endpoints of class k's synthetic self-edge — the class's
 // attribute pair, everything else zero, so that the edge features come out as a real self-loop's: [a, a, |0 - 0|, 0 - 0 ...] (written by thread k).
 __device__ __forceinline__ void ag_edge_node_tab_row(const float *state, const float *attrs, const float *p_instance, int n_inst, int n_p,
@@ -525,7 +528,7 @@ void ag_launch_message_fwd(const float *eterm, const float *hr, const float *hs,
                            long long N, int D, hipStream_t s);
 void ag_launch_message_bwd(const float *eterm, const float *hr, const float *hs, const int *row_ptr, const int *send,
                            const float *g_agg, float *g_e, float *g_hr, long long N, int D, hipStream_t s);
-// training chains (ag_mlp.hip): kind 0 = relation_encoder + W_rp[:, :F], 1 = particle_encoder, 2 = non_rigid_predictor
+// training chains (ag_chain.hip): kind 0 = relation_encoder + W_rp[:, :F], 1 = particle_encoder, 2 = non_rigid_predictor
 struct AgChainArgsPOD { const float *x; const float *w; float *y[4]; const float *dy; float *dz[4]; float *dx; long long rows; int d_in; };
 void ag_launch_train_pack(const float *W, const float *bias, int n_out, int n_in, int ld, int col0, int transposed, int compact,
                           int n_tiles, int b3, float *dst, hipStream_t s);

@@ -1,6 +1,6 @@
 // ag_train.hip — graph kernels of the TRAINING path: the gather / segment-reduce pieces of
 // DynamicsPredictor.forward (src/dynamics/gnn/model.py:220-295) and their adjoints, on the CSR adjacency, and the
-// weight-gradient reduction of the fused dense chains (the chains themselves: ag_mlp.hip).
+// weight-gradient reduction of the fused dense chains (the chains themselves: ag_chain.hip).
 //
 // The reference trains with one-hot Rr/Rs `bmm`s, whose autograd is again dense bmm.  Here the forward gathers rows by
 // index and segment-reduces messages over receiver-sorted edges, and the backward is the transposed pair: gradients
@@ -70,7 +70,7 @@ __global__ __launch_bounds__(256) void message_bwd_kernel(const float *eterm, co
     g_hr[t] = acc;
 }
 
-// ---- weight gradients of the fused dense chains (ag_mlp.hip: chain_backward_kernel) ---------------------------------------
+// ---- weight gradients of the fused dense chains (ag_chain.hip: chain_backward_kernel) ---------------------------------------
 // dW_l[o][k] = sum_rows dz_l[row][o] * prev_l[row][k]  and  db_l[o] = sum_rows dz_l[row][o]   (prev_l = input of layer l).
 // The shape defeats library GEMMs: a 150 x 150 output contracted over 10^4..10^5 rows has 25 output tiles, so hipBLASLt ran
 // it on 25 workgroups (88 us per layer, 4.2 of the 10.9 ms training step, profiles/r02_train_trace.txt).  Here the ROWS are split into

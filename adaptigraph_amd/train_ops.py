@@ -146,7 +146,7 @@ def message_sum(eterm, hr, hs, views):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# Dense stacks on the fused MFMA kernels (csrc/ag_mlp.hip: chain_forward_kernel / chain_backward_kernel)
+# Dense stacks on the fused MFMA kernels (csrc/ag_chain.hip: chain_forward_kernel / chain_backward_kernel)
 # ---------------------------------------------------------------------------------------------------------------------
 AG_FP, _ROW_TILE, _CHUNK = 160, 128, 5120
 CHAIN_KINDS = {"edge": (0, 4), "node": (1, 3), "decoder": (2, 3)}      # name -> (AG_CHAIN_*, layers)

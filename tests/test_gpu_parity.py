@@ -380,7 +380,7 @@ def test_fused_segment_reduce_equals_the_separate_kernel(weights):
 @pytest.mark.parametrize("case", ["rope_gap", "distinct_actions", "granular_tools", "cloth_padded", "ten_classes"])
 def test_node_encoder_deduplication_is_bitwise_the_per_node_encoder(weights, prec, case):
     """ag_set_option("node_dedup", 1) (default): particle_encode / Pn / the first round's Hr, Hs are computed once per distinct
-    [attrs | phys | action] row of a sample and read through an index (csrc/ag_mlp.hip node_classify_kernel).  Outputs must equal the
+    [attrs | phys | action] row of a sample and read through an index (csrc/ag_node_encode.hip node_classify_kernel).  Outputs must equal the
     per-node encoder bit for bit — with the usual two classes (objects, tool), with a private row for EVERY node (distinct actions),
     with several tools, padded slots, and more distinct rows than the shared slots per sample."""
     mat = {"rope_gap": "rope", "distinct_actions": "rope", "granular_tools": "granular", "cloth_padded": "cloth", "ten_classes": "rope"}[case]

@@ -37,7 +37,7 @@ def forward(g, wq, xq, first, node=False, hsq=None, hrq=None, groups=None, etq=N
         for i in (0, 2, 4): x = F.relu(lin(x, W[f"particle_encoder.model.{i}.weight"], W[f"particle_encoder.model.{i}.bias"], G('pe')))
         enc_n = x
         x = rel
-        if res_cols and first:      # r03: the last inputs (x_r - x_s) carry their fp16 residual in spare K slots of layer 1 (ag_mlp.hip f16_residual)
+        if res_cols and first:      # r03: the last inputs (x_r - x_s) carry their fp16 residual in spare K slots of layer 1 (ag_mlp_dev.h f16_residual)
             xe = xq(x); xe[:, -res_cols:] = xe[:, -res_cols:] + xq(x[:, -res_cols:] - xe[:, -res_cols:])
             x = F.relu(F.linear(xe, wq(W["relation_encoder.model.0.weight"]), W["relation_encoder.model.0.bias"]))
         else:
