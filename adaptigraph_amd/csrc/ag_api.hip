@@ -692,6 +692,29 @@ int ag_chamfer_backward(const float *x, const uint8_t *x_mask, const float *y, c
     return AG_OK;
 }
 
+// kept distances of the streaming form: one float per point of every cloud (asked of every call, so that the caller's buffer never depends on which
+// form the library picks for a size)
+size_t ag_fps_workspace_bytes(int B, int N)
+{
+    if (B < 1 || N < 1) return 0;
+    return align_up((size_t)B * (size_t)N * sizeof(float), 256);
+}
+
+int ag_fps(const float *pts, const int32_t *count, const int32_t *start, int B, int N, int K, int metric, const double *radius, int32_t *idx,
+           int32_t *n_out, void *workspace, size_t workspace_bytes, ag_stream_t stream)
+{
+    if (!pts || !start || !idx || !n_out) return fail(AG_ERR_ARG, "ag_fps: null argument");
+    if (B < 1 || N < 1 || K < 1) return fail(AG_ERR_ARG, "ag_fps: bad sizes B=%d N=%d K=%d", B, N, K);
+    if (metric != AG_FPS_SQUARED && metric != AG_FPS_NORM) return fail(AG_ERR_ARG, "ag_fps: unknown metric %d", metric);
+    if (radius && metric != AG_FPS_NORM) return fail(AG_ERR_ARG, "ag_fps: a radius stop needs AG_FPS_NORM (the radius is a distance, not a squared one)");
+    const size_t need = ag_fps_workspace_bytes(B, N);
+    if (!workspace || workspace_bytes < need)
+        return fail(AG_ERR_ARG, "ag_fps: workspace of %zu bytes, ag_fps_workspace_bytes(%d, %d) = %zu", workspace ? workspace_bytes : (size_t)0, B, N, need);
+    ag_launch_fps(pts, count, start, B, N, K, metric, radius, idx, n_out, static_cast<float *>(workspace), static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 int ag_gather_rows(const float *x, const int32_t *idx, float *out, int64_t n_out, int D, ag_stream_t stream)
 {
     if (n_out < 0 || D < 1) return fail(AG_ERR_ARG, "ag_gather_rows: bad sizes n_out=%lld D=%d", (long long)n_out, D);

@@ -542,6 +542,9 @@ size_t ag_weight_grads_ws_floats(long long rows, int n_layers);
 void ag_launch_weight_grads(int n_layers, const float *const *dz, const int *dz_ld, const float *const *prev, const int *prev_ld, const int *n_in,
                             long long rows, float *partial, float *out, float *const *w_dst, const int *w_ld, float *const *b_dst, const int *n_out,
                             hipStream_t s);
+// farthest-point sampling (ag_fps.hip): one workgroup per cloud; near_ws (B, N) floats is touched by the streaming form (N > AG_FPS_RESIDENT_POINTS) only
+void ag_launch_fps(const float *pts, const int32_t *count, const int32_t *start, int B, int N, int K, int metric, const double *radius,
+                   int32_t *idx, int32_t *n_out, float *near_ws, hipStream_t s);
 int ag_launch_chamfer(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,
                       int y_batched, float *out, hipStream_t s);
 int ag_launch_chamfer_idx(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,

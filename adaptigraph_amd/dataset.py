@@ -17,9 +17,12 @@ from .train_ops import EdgeViews
 
 
 class DynDataset(Dataset):
-    def __init__(self, dataset_config, material_config, phase="train"):
+    def __init__(self, dataset_config, material_config, phase="train", fps_device=None):
+        """`fps_device` (e.g. "cuda:0"): the key-point sampling of every item runs on that GPU (`sampling.fps(..., device=)`: the same indices and
+        RNG draws as the host code).  Meant for `DataLoader(num_workers=0)`: a worker process must not inherit an initialised GPU."""
         assert phase in ["train", "valid"]
         self.phase = phase
+        self.fps_device = fps_device
         self.dataset_config, self.material_config = dataset_config, material_config
         self.verbose = dataset_config.get("verbose", False)
         self.n_his, self.n_future = dataset_config["n_his"], dataset_config["n_future"]
@@ -49,7 +52,7 @@ class DynDataset(Dataset):
         assert len(pair) == H + Fu
         obj_kps = np.asarray(self.obj_pos[epi])[pair]            # (H+Fu, N_all, 3)
         eef_kps = np.asarray(self.eef_pos[epi])[pair]            # (H+Fu, N_eef, 3)
-        fps_idx = fps(obj_kps[H - 1], self.max_nobj, self.fps_radius_range, verbose=self.verbose)
+        fps_idx = fps(obj_kps[H - 1], self.max_nobj, self.fps_radius_range, verbose=self.verbose, device=self.fps_device)
         n_kp, n_eef = len(fps_idx), eef_kps.shape[1]
 
         kp = np.zeros((H + Fu, no, self.pos_dim), np.float32)    # sampled key-points of every frame, zero-padded

@@ -16,7 +16,7 @@ import torch
 
 from .graph import build_edges, construct_edges_from_states
 from .load import load_dataset, load_positions
-from .sampling import fps
+from .sampling import fps, fps_batch
 
 ROLLOUT_STEPS = 100      # rollout.py:62
 
@@ -45,14 +45,16 @@ def _dataset_params(dataset_config):
                 connect_tool_all=d["connect_tool_all"])
 
 
-def start_graph_arrays(dataset_config, material_config, eef_pos, obj_pos, n_his, pair):
-    """Host half of construct_graph: numpy arrays of everything but the edges.  -> (dict, fps_idx_list)."""
+def start_graph_arrays(dataset_config, material_config, eef_pos, obj_pos, n_his, pair, fps_device=None, fps_idx=None):
+    """Host half of construct_graph: numpy arrays of everything but the edges.  -> (dict, fps_idx_list).
+    `fps_device`: run the key-point sampling on that GPU (`sampling.fps(..., device=)`: same indices, same RNG draws); `fps_idx`: a ready index
+    list (from `sampling.fps_batch` over many start graphs) — nothing is sampled and nothing is drawn here."""
     P = _dataset_params(dataset_config)
     max_nobj, n_eef = P["max_nobj"], eef_pos.shape[1]
     n_state = max_nobj + n_eef
     frames = np.asarray(pair)
     obj_kps, eef_kps = np.asarray(obj_pos)[frames], np.asarray(eef_pos)[frames]
-    fps_idx_list = fps(obj_kps[n_his - 1], max_nobj, P["fps_radius"])
+    fps_idx_list = fps(obj_kps[n_his - 1], max_nobj, P["fps_radius"], device=fps_device) if fps_idx is None else np.asarray(fps_idx)
     n_kp = len(fps_idx_list)
 
     state_history = np.zeros((n_his, n_state, obj_kps.shape[-1]), np.float32)
@@ -81,12 +83,14 @@ def start_graph_arrays(dataset_config, material_config, eef_pos, obj_pos, n_his,
     return arrays, fps_idx_list
 
 
-def construct_graph(dataset_config, material_config, eef_pos, obj_pos, n_his, pair, physics_param, device="cuda"):
+def construct_graph(dataset_config, material_config, eef_pos, obj_pos, n_his, pair, physics_param, device="cuda", fps_device=None,
+                    fps_idx=None):
     """Start graph of one frame pair (graph.py:233-371): FPS key-points of frame pair[n_his-1], history from pair[:n_his],
     tool motion pair[n_his-1] -> pair[n_his], everything padded to max_nobj / max_nR, tensors on `device`.
-    -> (graph dict with the reference's keys, fps_idx_list)."""
+    -> (graph dict with the reference's keys, fps_idx_list).  `fps_device` / `fps_idx`: see start_graph_arrays."""
     P = _dataset_params(dataset_config)
-    arrays, fps_idx_list = start_graph_arrays(dataset_config, material_config, eef_pos, obj_pos, n_his, pair)
+    arrays, fps_idx_list = start_graph_arrays(dataset_config, material_config, eef_pos, obj_pos, n_his, pair, fps_device=fps_device,
+                                              fps_idx=fps_idx)
     dev = torch.device(device)
     graph = {k: torch.from_numpy(v).to(dev) for k, v in arrays.items()}
     Rr, Rs = construct_edges_from_states(graph["state"][-1], P["adj_thresh"], graph["state_mask"], graph["eef_mask"], P["topk"],
@@ -180,43 +184,63 @@ def rollout_from_start_graph(graph, fps_idx_list, dataset_config, material_confi
     return rollout_batch(model, device, [graph], [fps_idx_list], [sched], [eef_pos], [obj_pos], dataset_config)[0]
 
 
-def _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param, device):
-    """Start graph + frame schedule of every push of an episode (the first row of each push file), rollout.py:149-165."""
-    n_his = dataset_config["n_his"]
+def _episode_first_pairs(dataset_config, episode_idx):
+    """The frame pair every push of an episode starts from: the first row of each push file, in file order."""
     pairs_path = os.path.join(dataset_config["prep_data_dir"], dataset_config["data_name"], "frame_pairs")
+    return [np.loadtxt(path).astype(int)[0] for path in sorted(glob.glob(os.path.join(pairs_path, f"{episode_idx:06}_*.txt")))]
+
+
+def _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param, device, fps_device=None,
+                    fps_idx_lists=None):
+    """Start graph + frame schedule of every push of an episode (the first row of each push file), rollout.py:149-165.
+    `fps_idx_lists`: one ready key-point index list per push (rollout_dataset samples all start graphs in one batch)."""
+    n_his = dataset_config["n_his"]
     out = []
-    for path in sorted(glob.glob(os.path.join(pairs_path, f"{episode_idx:06}_*.txt"))):
-        pair = np.loadtxt(path).astype(int)[0]
+    for i, pair in enumerate(_episode_first_pairs(dataset_config, episode_idx)):
         eef_epi, obj_epi = eef_pos[episode_idx], obj_pos[episode_idx]
         graph, fps_idx_list = construct_graph(dataset_config, material_config, eef_epi, obj_epi, n_his, pair, physics_param,
-                                              device=device)
+                                              device=device, fps_device=fps_device,
+                                              fps_idx=None if fps_idx_lists is None else fps_idx_lists[i])
         sched = frame_schedule(pairs, n_his, obj_epi.shape[0], pair[n_his - 1], pair[n_his], get_next_pair_or_break_episode_pushes)
         out.append((graph, fps_idx_list, sched, eef_epi, obj_epi))
     return out
 
 
 def rollout_episode_pushes(model, device, dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param,
-                           save_dir, viz=False, imgs=None, cam_info=None):
+                           save_dir, viz=False, imgs=None, cam_info=None, fps_device=None):
     """-> [error list per push]; writes error_<i>.txt per push like the reference (rollout.py:145-196; no plots/videos)."""
-    starts = _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param, device)
+    starts = _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param, device,
+                             fps_device=fps_device)
     errs = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config) if starts else []
     for i, e in enumerate(errs):
         np.savetxt(os.path.join(save_dir, f"error_{i + 1}.txt"), np.array(e))
     return errs
 
 
-def rollout_dataset(model, device, config, save_dir, viz=False):
+def rollout_dataset(model, device, config, save_dir, viz=False, fps_device=None):
     """Validation split -> per-episode/per-push error files + error_short.txt (steps x pushes, truncated to the shortest
-    rollout), rollout.py:198-265.  All pushes of all episodes run as ONE batch.  -> step_error array."""
+    rollout), rollout.py:198-265.  All pushes of all episodes run as ONE batch.  -> step_error array.
+    `fps_device`: the key-point sampling of EVERY start graph runs there as one `fps_batch` call (one launch per pass for the whole split).
+    Building a start graph draws nothing but its sampling's numbers from the RNG, so the draws come in the same order and the start graphs
+    are the same as with the per-graph host sampling."""
     dataset_config, material_config = config["dataset_config"], config["material_config"]
     pair_lists, physics_params = load_dataset(dataset_config, material_config, phase="valid")
     pair_lists = np.array(pair_lists)
     eef_pos, obj_pos = load_positions(dataset_config)
     starts, owners = [], []
-    for episode_idx in sorted(np.unique(pair_lists[:, 0]).astype(int)):
+    episodes = sorted(np.unique(pair_lists[:, 0]).astype(int))
+    fps_idx = {}
+    if fps_device is not None:
+        n_his = dataset_config["n_his"]
+        first = {e: _episode_first_pairs(dataset_config, e) for e in episodes}
+        frames = [np.asarray(obj_pos[e])[pair[n_his - 1]] for e in episodes for pair in first[e]]
+        P = _dataset_params(dataset_config)
+        lists = iter(fps_batch(frames, P["max_nobj"], P["fps_radius"], fps_device))
+        fps_idx = {e: [next(lists) for _ in first[e]] for e in episodes}
+    for episode_idx in episodes:
         pairs_epi = pair_lists[pair_lists[:, 0] == episode_idx][:, 1:]
         epi = _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs_epi, physics_params[episode_idx],
-                              device)
+                              device, fps_idx_lists=fps_idx.get(episode_idx))
         starts.extend(epi)
         owners.extend((episode_idx, i + 1) for i in range(len(epi)))
     total = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config)
@@ -245,4 +269,4 @@ def rollout(config, epoch, viz=False):
     model = DynamicsPredictor(config["model_config"], config["material_config"], dataset_config, device)
     model.to(device).eval()
     model.load_state_dict(torch.load(os.path.join(train_config["out_dir"], data_name, "checkpoints", ckpt), map_location=device))
-    return rollout_dataset(model, device, config, save_dir, viz)
+    return rollout_dataset(model, device, config, save_dir, viz, fps_device=config["rollout_config"].get("fps_device"))

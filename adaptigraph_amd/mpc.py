@@ -59,7 +59,8 @@ class Planner:
         self.clip_action_sequences = config.get("clip_action_seq_fn", self.clip_actions_default)
         self.optimize_action_mppi = config.get("optimize_action_mppi_fn", self.optimize_action_mppi_default)
         self.noise_type = config.get("noise_type", "normal")
-        assert self.noise_type == "normal", "only the 'normal' sampler is provided (the 'fps' grid sampler needs the reference's fps_np)"
+        assert self.noise_type == "normal", ("only the 'normal' sampler is provided: the 'fps' grid sampler runs farthest-point sampling on a float64 np.arange grid "
+                                             "(~1e10 points at the shipped action limits), whose ties the fp32 kernel ag_fps cannot reproduce")
         self.noise_level = config.get("noise_level", 0.1)
         self.n_his = config.get("n_his", 1)
         self.rollout_best = config.get("rollout_best", True)

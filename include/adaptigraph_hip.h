@@ -218,6 +218,26 @@ int ag_chamfer_fwd_idx(const float *x, const uint8_t *x_mask, const float *y, co
 int ag_chamfer_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x, const int32_t *idx_y,
                         const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy, ag_stream_t stream);
 
+/* ---- farthest-point key-point sampling (SURVEY.md §8f row n3 data side): the two passes of fps() of src/dynamics/dataset/graph.py:8-36 — the
+ * first is dgl.geometry.farthest_point_sampler, the second fps_rad_idx of src/dynamics/utils.py:10-24 — and with them the perception step of
+ * the closed loop, src/planning/perception.py:266-279.  B clouds in one launch, one workgroup per cloud.
+ *   pts (B,N,3) fp32; count (B) = number of valid LEADING points of each cloud, or NULL (all N); start (B) = index of the first pick.
+ * Per cloud: pick start[b]; keep for every point the distance to its nearest pick; the next pick is the arg-max of the kept distances, the
+ * LOWEST index on ties; stop after K picks, after count[b] picks, or — radius not NULL — as soon as the largest kept distance is <= radius[b]
+ * (the float32 distance compared with the double as doubles).  A cloud with count[b] < 1 or start[b] outside [0, count[b]) gets no pick.
+ * `metric` fixes the arithmetic (ties follow it), fp32 with every product and sum rounded separately, d = p - pick:
+ *   AG_FPS_SQUARED  (d0 d0 + d1 d1) + d2 d2                                   (farthest_point_sampler; radius must be NULL)
+ *   AG_FPS_NORM     the correctly rounded square root of that, per point      (fps_rad_idx: np.linalg.norm)
+ * Out: idx (B,K) int32 picks in order, -1 past the cloud's last pick; n_out (B) picks made.
+ * Clouds of up to AG_FPS_RESIDENT_POINTS points are held in registers for the whole call; larger ones stream the points from global memory
+ * and keep the distances in `workspace` (ag_fps_workspace_bytes(B, N), asked of every call): there is no size limit.  Inputs are assumed
+ * finite (a NaN or infinite coordinate gives unspecified picks, never an out-of-range index).  No host synchronisation: safe to capture. */
+enum { AG_FPS_SQUARED = 0, AG_FPS_NORM = 1 };
+#define AG_FPS_RESIDENT_POINTS 8192
+size_t ag_fps_workspace_bytes(int B, int N);
+int ag_fps(const float *pts, const int32_t *count, const int32_t *start, int B, int N, int K, int metric, const double *radius,
+           int32_t *idx, int32_t *n_out, void *workspace, size_t workspace_bytes, ag_stream_t stream);
+
 /* ---- training path: graph pieces of DynamicsPredictor.forward and their adjoints on the CSR adjacency.
  * Plain row-major fp32 tensors of arbitrary feature width D; every reduction runs in a fixed order (no atomics).
  *
