@@ -206,8 +206,12 @@ _ZEROS = {}
 
 
 def _zero_padded(tag, rows_pad, dev):
-    """A (rows_pad, 160) fp32 buffer whose every element outside the block a caller overwrites is zero.  One per (tag, shape):
-    callers overwrite the SAME live block each time and consume the buffer on the same stream before the next use."""
+    """A (rows_pad, 160) fp32 buffer, zero when created and shared by every call with the same (tag, shape); each caller
+    overwrites its own live block [:rows, :n_out] and consumes the buffer on the same stream before the next use.  Columns
+    >= n_out stay zero.  Rows >= `rows` are zero only until a call with MORE rows at the same padded size has run: afterwards
+    they hold that call's values.  That is harmless: the chain kernels treat every row on its own, dx is written (or sliced)
+    up to `rows` only and the weight-gradient kernel never reads a row >= `rows`
+    (tests/test_train_kernels.py::test_chain_backward_ignores_stale_rows_of_the_shared_dy_buffer)."""
     key = (tag, rows_pad, dev.index)
     buf = _ZEROS.get(key)
     if buf is None:
@@ -232,8 +236,10 @@ class _FusedChain(torch.autograd.Function):
         if kind == "decoder":
             xin = x.new_zeros((rows_pad, AG_FP))                    # saved for the backward: a fresh table per call
             xin[:rows, : x.shape[1]] = x
-        else:
+        elif rows:
             xin = x.contiguous().float()
+        else:                                                       # an empty tensor has a null data pointer, which the C ABI refuses
+            xin = torch.zeros((1, x.shape[1]), dtype=torch.float32, device=dev)
         ys = [torch.empty((rows_pad, AG_FP), dtype=torch.float32, device=dev) for _ in range(n)]
         with torch.cuda.device(dev):
             rc = _lib.lib().ag_train_chain(code, 0, prec, xin.data_ptr(), fwd.data_ptr(), _ptr_array(ys), None, _ptr_array([]), None, rows,
