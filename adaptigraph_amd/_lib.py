@@ -16,7 +16,7 @@ EXPORTS = ("ag_last_error", "ag_version", "ag_model_create", "ag_model_update_we
            "ag_forward", "ag_rollout_workspace_bytes", "ag_rollout", "ag_profile_enable", "ag_profile_read", "ag_set_option", "ag_chamfer", "ag_chamfer_masked", "ag_gather_rows", "ag_segment_sum",
            "ag_message_forward", "ag_message_backward", "ag_model_status", "ag_train_pack", "ag_train_chain", "ag_train_weight_grads", "ag_train_weight_grads_workspace_bytes", "ag_add3_relu", "ag_relu_mask", "ag_train_weight_grads_into", "ag_edge_inputs_forward", "ag_edge_inputs_backward",
            "ag_forward_workspace_bytes_for", "ag_rollout_workspace_bytes_for", "ag_rollout_streams_for", "ag_get_option",
-           "ag_chamfer_fwd_idx", "ag_chamfer_backward", "ag_fps", "ag_fps_workspace_bytes")
+           "ag_chamfer_fwd_idx", "ag_chamfer_backward", "ag_fps", "ag_fps_workspace_bytes", "ag_gather_clouds", "ag_assemble_batch")
 KERNEL_CLASSES = ("build_edges", "node_encode", "edge_encode", "aggregate", "node_update", "rollout_step")
 
 AG_VARIANT_SINGLE, AG_VARIANT_BATCH = 0, 1
@@ -30,6 +30,15 @@ class ModelConfig(ctypes.Structure):
     _fields_ = [("nf", ctypes.c_int32), ("n_his", ctypes.c_int32), ("attr_dim", ctypes.c_int32),
                 ("phys_dim", ctypes.c_int32), ("action_dim", ctypes.c_int32), ("pstep", ctypes.c_int32),
                 ("motion_clamp", ctypes.c_float)]
+
+
+class BatchDims(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "H", "Fu", "no", "n_eef", "K", "n_mat", "mat_col", "n_episodes", "tool_f64")]
+
+
+class BatchOut(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("state", "action", "eef_future", "action_future", "state_future", "attrs", "p_instance", "obj_mask",
+                                               "state_mask", "eef_mask", "material_index")]
 
 
 class RolloutParams(ctypes.Structure):
@@ -116,6 +125,10 @@ def lib():
     L.ag_fps_workspace_bytes.argtypes = [c_int, c_int]
     L.ag_fps.restype = c_int
     L.ag_fps.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
+    L.ag_gather_clouds.restype = c_int
+    L.ag_gather_clouds.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
+    L.ag_assemble_batch.restype = c_int
+    L.ag_assemble_batch.argtypes = [ctypes.POINTER(BatchDims)] + [c_void_p] * 8 + [ctypes.POINTER(BatchOut), c_void_p]
     L.ag_train_pack.restype = c_int
     L.ag_train_pack.argtypes = [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]
     L.ag_train_chain.restype = c_int

@@ -715,6 +715,48 @@ int ag_fps(const float *pts, const int32_t *count, const int32_t *start, int B, 
     return AG_OK;
 }
 
+int ag_gather_clouds(const float *obj_store, const int64_t *episodes, int n_episodes, const int32_t *epi, const int32_t *frame, int B, int Nmax,
+                     float *pts, int32_t *count, ag_stream_t stream)
+{
+    const struct { const void *p; const char *name; } ptrs[] = {{obj_store, "obj_store"}, {episodes, "episodes"}, {epi, "epi"}, {frame, "frame"},
+                                                                {pts, "pts"}, {count, "count"}};
+    for (const auto &a : ptrs)
+        if (!a.p) return fail(AG_ERR_ARG, "ag_gather_clouds: %s is null", a.name);
+    if (n_episodes < 1 || B < 1 || B > 65535 || Nmax < 1)
+        return fail(AG_ERR_ARG, "ag_gather_clouds: bad sizes n_episodes=%d B=%d (1..65535) Nmax=%d", n_episodes, B, Nmax);
+    ag_launch_gather_clouds(obj_store, episodes, n_episodes, epi, frame, B, Nmax, pts, count, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_assemble_batch(const ag_batch_dims *dims, const float *obj_store, const void *tool_store, const int64_t *episodes, const int32_t *epi,
+                      const int32_t *frames, const int32_t *picks, const double *noise, const float *rot, const ag_batch_out *out,
+                      ag_stream_t stream)
+{
+    if (!dims) return fail(AG_ERR_ARG, "ag_assemble_batch: dims is null");
+    if (!out) return fail(AG_ERR_ARG, "ag_assemble_batch: out is null");
+    const ag_batch_dims &d = *dims;
+    if (d.B < 1 || d.B > 65535 || d.H < 1 || d.Fu < 1 || d.H + d.Fu > 65535 || d.no < 1 || d.n_eef < 1 || d.K < 1 || d.n_episodes < 1)
+        return fail(AG_ERR_ARG, "ag_assemble_batch: bad sizes B=%d (1..65535) H=%d Fu=%d no=%d n_eef=%d K=%d n_episodes=%d", d.B, d.H, d.Fu, d.no,
+                    d.n_eef, d.K, d.n_episodes);
+    if (d.n_mat < 1 || d.mat_col < 0 || d.mat_col >= d.n_mat)
+        return fail(AG_ERR_ARG, "ag_assemble_batch: mat_col=%d outside n_mat=%d", d.mat_col, d.n_mat);
+    if ((noise == nullptr) != (rot == nullptr))
+        return fail(AG_ERR_ARG, "ag_assemble_batch: give both noise and rot or neither (%s is null)", noise ? "rot" : "noise");
+    const bool futures = d.Fu > 1;      // with Fu == 1 the two (B, Fu - 1, ns, 3) tensors are empty
+    const struct { const void *p; const char *name; bool needed; } ptrs[] = {
+        {obj_store, "obj_store", true}, {tool_store, "tool_store", true}, {episodes, "episodes", true}, {epi, "epi", true}, {frames, "frames", true},
+        {picks, "picks", true}, {out->state, "out.state", true}, {out->action, "out.action", true}, {out->eef_future, "out.eef_future", futures},
+        {out->action_future, "out.action_future", futures}, {out->state_future, "out.state_future", true}, {out->attrs, "out.attrs", true},
+        {out->p_instance, "out.p_instance", true}, {out->obj_mask, "out.obj_mask", true}, {out->state_mask, "out.state_mask", true},
+        {out->eef_mask, "out.eef_mask", true}, {out->material_index, "out.material_index", true}};
+    for (const auto &a : ptrs)
+        if (a.needed && !a.p) return fail(AG_ERR_ARG, "ag_assemble_batch: %s is null", a.name);
+    ag_launch_assemble_batch(d, obj_store, tool_store, episodes, epi, frames, picks, noise, rot, *out, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 int ag_gather_rows(const float *x, const int32_t *idx, float *out, int64_t n_out, int D, ag_stream_t stream)
 {
     if (n_out < 0 || D < 1) return fail(AG_ERR_ARG, "ag_gather_rows: bad sizes n_out=%lld D=%d", (long long)n_out, D);

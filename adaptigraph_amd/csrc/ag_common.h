@@ -545,6 +545,13 @@ void ag_launch_weight_grads(int n_layers, const float *const *dz, const int *dz_
 // farthest-point sampling (ag_fps.hip): one workgroup per cloud; near_ws (B, N) floats is touched by the streaming form (N > AG_FPS_RESIDENT_POINTS) only
 void ag_launch_fps(const float *pts, const int32_t *count, const int32_t *start, int B, int N, int K, int metric, const double *radius,
                    int32_t *idx, int32_t *n_out, float *near_ws, hipStream_t s);
+// training batches on the device (ag_batch.hip): the padded clouds of one frame per sample, and every per-item tensor of the collated batch
+struct ag_batch_dims;
+struct ag_batch_out;
+void ag_launch_gather_clouds(const float *store, const int64_t *episodes, int n_episodes, const int32_t *epi, const int32_t *frame, int B, int Nmax,
+                             float *pts, int32_t *count, hipStream_t s);
+void ag_launch_assemble_batch(const ag_batch_dims &d, const float *obj, const void *tool, const int64_t *episodes, const int32_t *epi,
+                              const int32_t *frames, const int32_t *picks, const double *noise, const float *rot, const ag_batch_out &o, hipStream_t s);
 int ag_launch_chamfer(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,
                       int y_batched, float *out, hipStream_t s);
 int ag_launch_chamfer_idx(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,

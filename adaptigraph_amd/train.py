@@ -15,7 +15,7 @@ from torch.utils.data import DataLoader
 
 from . import train_ops
 
-from .dataset import DynDataset, attach_edges
+from .dataset import DeviceBatcher, DynDataset, attach_edges
 from .train_model import TrainableDynamicsPredictor, unrolled_loss
 
 
@@ -32,8 +32,23 @@ def _cycle(loader):
             yield batch
 
 
+class _Indices(torch.utils.data.Dataset):
+    """The index-only stand-in for a dataset: the DataLoader batches and shuffles sample numbers, DeviceBatcher turns them into tensors."""
+
+    def __init__(self, n):
+        self.n = n
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, idx):
+        return idx
+
+
 def train(config):
-    """-> {'train': [mean logged loss per epoch], 'valid': [...]}."""
+    """-> {'train': [mean logged loss per epoch], 'valid': [...]}.
+    train_config['device_batches'] (default false): the batches are assembled on the GPU from positions resident in HBM (`DeviceBatcher`): same
+    DataLoader sample order and same values as the host loader with num_workers=0 under the same seed."""
     dataset_config, train_config = config["dataset_config"], config["train_config"]
     model_config, material_config = config["model_config"], config["material_config"]
     data_name = dataset_config["data_name"]
@@ -46,8 +61,14 @@ def train(config):
 
     n_future, phases = dataset_config["n_future"], train_config["phases"]
     datasets = {ph: DynDataset(dataset_config, material_config, phase=ph) for ph in phases}
-    loaders = {ph: _cycle(DataLoader(datasets[ph], batch_size=train_config["batch_size"], shuffle=(ph == "train"),
-                                     num_workers=train_config["num_workers"])) for ph in phases}
+    if train_config.get("device_batches", False):
+        batchers = {ph: DeviceBatcher(datasets[ph], device) for ph in phases}
+        index_loaders = {ph: _cycle(DataLoader(_Indices(len(datasets[ph])), batch_size=train_config["batch_size"], shuffle=(ph == "train"),
+                                               num_workers=0)) for ph in phases}
+        loaders = {ph: map(lambda idx, batcher=batchers[ph]: batcher.batch(idx.tolist()), index_loaders[ph]) for ph in phases}
+    else:
+        loaders = {ph: _cycle(DataLoader(datasets[ph], batch_size=train_config["batch_size"], shuffle=(ph == "train"),
+                                         num_workers=train_config["num_workers"])) for ph in phases}
     model = TrainableDynamicsPredictor(model_config, material_config, dataset_config, device).to(device)
     optimizer = torch.optim.Adam(model.parameters(), lr=0.001)
 

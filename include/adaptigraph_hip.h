@@ -238,6 +238,48 @@ size_t ag_fps_workspace_bytes(int B, int N);
 int ag_fps(const float *pts, const int32_t *count, const int32_t *start, int B, int N, int K, int metric, const double *radius,
            int32_t *idx, int32_t *n_out, void *workspace, size_t workspace_bytes, ag_stream_t stream);
 
+/* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
+ * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
+ *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
+ *   tool_store  the tool positions (T_e, n_eef, 3) likewise, fp32 or — dims.tool_f64 — float64 (the dataset's own dtype: the actions are
+ *               differences taken in that dtype and rounded to fp32 afterwards)
+ *   episodes    (n_episodes, 4) int64: first point of the episode in obj_store, first point in tool_store, T_e, N_e
+ *   epi (B) int32 episode of every sample; all of these are DEVICE arrays, nothing is read back.
+ *
+ * ag_gather_clouds: pts[b, :N, :] = frame frame[b] of episode epi[b], zeros behind, N = min(N_e, Nmax); count[b] = N: the padded clouds
+ *   ag_fps pass 1 takes.  A sample whose episode or frame is out of range gets count 0.
+ *
+ * ag_assemble_batch: every per-item tensor of the collated batch in one launch, ns = no + n_eef nodes per sample (objects first):
+ *   frames (B, H + Fu) int32 frame of every history / future slot; picks (B, K + 1) int32 as sampling.two_pass_tensors returns them: the
+ *   key-point indices into the cloud, -1 behind the last, their number n_kp in column K (read on the device).
+ *   state (B,H,ns,3): rows < n_kp the picked points, rows >= no the tool points, zeros between;  state_future (B,Fu,no,3) likewise (objects);
+ *   eef_future (B,Fu-1,ns,3) the tool rows of future slot f;  action (B,ns,3) = tool[H] - tool[H-1], action_future (B,Fu-1,ns,3) =
+ *   tool[H+f+1] - tool[H+f] (tool rows; object rows zero);  attrs (B,ns,2) = [row < n_kp, row >= no];  p_instance (B,no,1), obj_mask (B,no)
+ *   = row < n_kp;  state_mask (B,ns) = row < n_kp or row >= no;  eef_mask (B,ns) = row >= no (masks: one byte, 0 / 1);
+ *   material_index (B,no,n_mat) int64 = 1 at column mat_col of rows < n_kp.  With Fu == 1 eef_future / action_future are empty and may be NULL.
+ *   noise (B,H,ns,3) float64 and rot (B,3,3) fp32, both or neither (dataset.py:184-195, randomness.use): state = fp32(double(state) + noise),
+ *   one rounding, on every row; then every position tensor (state, state_future, eef_future, action, action_future) becomes a @ rot[b],
+ *   out_j = fmaf(a2, r2j, fmaf(a1, r1j, a0 * r0j)).
+ * An index outside its table (episode, frame, pick) yields zeros, never an out-of-range read.  No host synchronisation: safe to capture. */
+typedef struct ag_batch_dims {
+    int32_t B, H, Fu;         /* samples, n_his, n_future */
+    int32_t no, n_eef;        /* max_nobj, tool points */
+    int32_t K;                /* picks has K + 1 columns */
+    int32_t n_mat, mat_col;   /* material_index width and the column set */
+    int32_t n_episodes;
+    int32_t tool_f64;         /* tool_store holds doubles */
+} ag_batch_dims;
+typedef struct ag_batch_out {
+    float *state, *action, *eef_future, *action_future, *state_future, *attrs, *p_instance;
+    uint8_t *obj_mask, *state_mask, *eef_mask;
+    int64_t *material_index;
+} ag_batch_out;
+int ag_gather_clouds(const float *obj_store, const int64_t *episodes, int n_episodes, const int32_t *epi, const int32_t *frame, int B, int Nmax,
+                     float *pts, int32_t *count, ag_stream_t stream);
+int ag_assemble_batch(const ag_batch_dims *dims, const float *obj_store, const void *tool_store, const int64_t *episodes, const int32_t *epi,
+                      const int32_t *frames, const int32_t *picks, const double *noise, const float *rot, const ag_batch_out *out,
+                      ag_stream_t stream);
+
 /* ---- training path: graph pieces of DynamicsPredictor.forward and their adjoints on the CSR adjacency.
  * Plain row-major fp32 tensors of arbitrary feature width D; every reduction runs in a fixed order (no atomics).
  *
