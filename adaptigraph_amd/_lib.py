@@ -16,7 +16,8 @@ EXPORTS = ("ag_last_error", "ag_version", "ag_model_create", "ag_model_update_we
            "ag_forward", "ag_rollout_workspace_bytes", "ag_rollout", "ag_profile_enable", "ag_profile_read", "ag_set_option", "ag_chamfer", "ag_chamfer_masked", "ag_gather_rows", "ag_segment_sum",
            "ag_message_forward", "ag_message_backward", "ag_model_status", "ag_train_pack", "ag_train_chain", "ag_train_weight_grads", "ag_train_weight_grads_workspace_bytes", "ag_add3_relu", "ag_relu_mask", "ag_train_weight_grads_into", "ag_edge_inputs_forward", "ag_edge_inputs_backward",
            "ag_forward_workspace_bytes_for", "ag_rollout_workspace_bytes_for", "ag_rollout_streams_for", "ag_get_option",
-           "ag_chamfer_fwd_idx", "ag_chamfer_backward", "ag_fps", "ag_fps_workspace_bytes", "ag_gather_clouds", "ag_assemble_batch")
+           "ag_chamfer_fwd_idx", "ag_chamfer_backward", "ag_fps", "ag_fps_workspace_bytes", "ag_gather_clouds", "ag_assemble_batch",
+           "ag_dense_edges_workspace_bytes", "ag_edges_from_dense", "ag_edges_to_dense")
 KERNEL_CLASSES = ("build_edges", "node_encode", "edge_encode", "aggregate", "node_update", "rollout_step")
 
 AG_VARIANT_SINGLE, AG_VARIANT_BATCH = 0, 1
@@ -90,6 +91,12 @@ def lib():
     L.ag_edges_workspace_bytes.argtypes = [c_int] * 5
     L.ag_build_edges.restype = c_int
     L.ag_build_edges.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p] * 3 + [c_int64, c_void_p, c_size_t, c_void_p]
+    L.ag_dense_edges_workspace_bytes.restype = c_size_t
+    L.ag_dense_edges_workspace_bytes.argtypes = [c_int] * 3
+    L.ag_edges_from_dense.restype = c_int
+    L.ag_edges_from_dense.argtypes = [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 4 + [c_size_t, c_void_p]
+    L.ag_edges_to_dense.restype = c_int
+    L.ag_edges_to_dense.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 4
     L.ag_forward_workspace_bytes.restype = c_size_t
     L.ag_forward_workspace_bytes.argtypes = [c_int, c_int, c_int64]
     L.ag_forward_workspace_bytes_for.restype = c_size_t

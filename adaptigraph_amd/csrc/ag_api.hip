@@ -388,6 +388,15 @@ void carve_edges(Carver &c, AgEdgeArgs &a)
     a.sorted = c.take<float4>(rows);
 }
 
+void carve_dense(Carver &c, AgDenseArgs &a)
+{
+    const size_t pairs = (size_t)a.B * a.E, rows = (size_t)a.B * a.N;
+    a.key_recv = c.take<int32_t>(pairs);
+    a.key_send = c.take<int32_t>(pairs);
+    a.cnt = c.take<int32_t>(rows);
+    a.blk_sum = c.take<int32_t>(rows / 256 + 2);       // one partial sum per 256 receivers (ag_dense.hip: kScanRows)
+}
+
 void edge_caps(int N, int topk, int connect, int max_tools, int *cap0, int *cap)
 {
     *cap0 = N < topk ? N : topk;
@@ -1012,6 +1021,46 @@ int ag_build_edges(const float *pos, const uint8_t *mask, const uint8_t *tool_ma
     carve_edges(c, a);
     if (!c.ok()) return fail(AG_ERR_WS, "ag_build_edges: workspace %zu < %zu bytes", workspace_bytes, c.off);
     ag_launch_build_edges(a, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+size_t ag_dense_edges_workspace_bytes(int B, int E, int N)
+{
+    if (B < 1 || E < 1 || N < 1) return 0;
+    AgDenseArgs a{};
+    a.B = B; a.E = E; a.N = N;
+    Carver c(nullptr, 0);
+    carve_dense(c, a);
+    return align_up(c.off, 256);
+}
+
+int ag_edges_from_dense(const float *Rr, const float *Rs, int B, int E, int N, int32_t *row_ptr, int32_t *edge_recv, int32_t *edge_send,
+                        void *workspace, size_t workspace_bytes, ag_stream_t stream)
+{
+    if (!Rr || !Rs || !row_ptr || !edge_recv || !edge_send || !workspace) return fail(AG_ERR_ARG, "ag_edges_from_dense: null argument");
+    if (B < 1 || E < 1 || N < 1) return fail(AG_ERR_ARG, "ag_edges_from_dense: bad sizes B=%d E=%d N=%d", B, E, N);
+    if ((int64_t)B * N >= (1ll << 31) - 1 || (int64_t)B * E >= (1ll << 31) - 1)
+        return fail(AG_ERR_ARG, "ag_edges_from_dense: B*N = %lld or B*E = %lld too large for int32 ids", (long long)B * N, (long long)B * E);
+    AgDenseArgs a{};
+    a.Rr = Rr; a.Rs = Rs; a.B = B; a.E = E; a.N = N;
+    a.row_ptr = row_ptr; a.edge_recv = edge_recv; a.edge_send = edge_send;
+    Carver c(workspace, workspace_bytes);
+    carve_dense(c, a);
+    if (!c.ok()) return fail(AG_ERR_WS, "ag_edges_from_dense: workspace %zu < %zu bytes", workspace_bytes, c.off);
+    ag_launch_edges_from_dense(a, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_edges_to_dense(const int32_t *row_ptr, const int32_t *edge_recv, const int32_t *edge_send, int B, int N, int E_out, float *Rr, float *Rs,
+                      int32_t *overflow, ag_stream_t stream)
+{
+    if (!row_ptr || !edge_recv || !edge_send || !Rr || !Rs || !overflow) return fail(AG_ERR_ARG, "ag_edges_to_dense: null argument");
+    if (B < 1 || N < 1 || E_out < 1) return fail(AG_ERR_ARG, "ag_edges_to_dense: bad sizes B=%d N=%d E_out=%d", B, N, E_out);
+    if ((int64_t)B * N >= (1ll << 31) - 1 || (int64_t)B * E_out >= (1ll << 31) - 1)
+        return fail(AG_ERR_ARG, "ag_edges_to_dense: B*N = %lld or B*E_out = %lld too large", (long long)B * N, (long long)B * E_out);
+    ag_launch_edges_to_dense(row_ptr, edge_recv, edge_send, B, N, E_out, Rr, Rs, overflow, static_cast<hipStream_t>(stream));
     AG_HIP(hipGetLastError());
     return AG_OK;
 }

@@ -545,6 +545,19 @@ void ag_launch_weight_grads(int n_layers, const float *const *dz, const int *dz_
 // farthest-point sampling (ag_fps.hip): one workgroup per cloud; near_ws (B, N) floats is touched by the streaming form (N > AG_FPS_RESIDENT_POINTS) only
 void ag_launch_fps(const float *pts, const int32_t *count, const int32_t *start, int B, int N, int K, int metric, const double *radius,
                    int32_t *idx, int32_t *n_out, float *near_ws, hipStream_t s);
+// dense one-hot relation matrices <-> CSR (ag_dense.hip): Rr, Rs (B, E, N) fp32 -> row_ptr (B N + 1), edge_recv / edge_send (B E), and back
+struct AgDenseArgs {
+    const float *Rr, *Rs;
+    int B, E, N;
+    int32_t *row_ptr, *edge_recv, *edge_send;
+    // workspace
+    int32_t *key_recv, *key_send;      // (B E) receiver slot of every row pair or -1, its sender slot
+    int32_t *cnt;                      // (B N) edges per receiver, then every receiver's write cursor
+    int32_t *blk_sum;                  // scan partials, one per 256 receivers
+};
+void ag_launch_edges_from_dense(const AgDenseArgs &a, hipStream_t s);
+void ag_launch_edges_to_dense(const int32_t *row_ptr, const int32_t *edge_recv, const int32_t *edge_send, int B, int N, int E_out, float *Rr,
+                              float *Rs, int32_t *overflow, hipStream_t s);
 // training batches on the device (ag_batch.hip): the padded clouds of one frame per sample, and every per-item tensor of the collated batch
 struct ag_batch_dims;
 struct ag_batch_out;

@@ -63,20 +63,45 @@ class CSREdges:
             out.append((r[lo:hi] - b * self.N, s[lo:hi] - b * self.N))
         return out
 
-    def to_dense(self, dtype=torch.float32):
-        """(Rr, Rs) one-hot (B, max n_rel, N) exactly as graph.py:146-155 lays them out (host sync)."""
-        n = self.n_rel()
-        e_max = int(n.max().item()) if self.B else 0
-        total = int(self.row_ptr[-1].item())
+    def to_dense(self, dtype=torch.float32, e_max=None):
+        """(Rr, Rs) one-hot (B, e_max, N) exactly as graph.py:146-155 lays them out, written by ag_edges_to_dense.
+
+        e_max=None: the batch maximum of n_rel, the reference's shape (one host read).  An integer e_max pads to that many rows — the
+        reference's pad_torch(Rr, max_nR) in the same step — with no host synchronisation (safe to capture); a sample with more edges
+        loses the surplus ones.  Either way `self.overflow` is then a device int32 word: 1 if some sample had more than e_max edges.
+        (An adjacency in host memory — csr_from_dense of CPU tensors — gets the same tensors from torch indexing.)"""
         dev = self.row_ptr.device
-        Rr = torch.zeros((self.B, e_max, self.N), dtype=dtype, device=dev)
-        Rs = torch.zeros((self.B, e_max, self.N), dtype=dtype, device=dev)
-        if total:
+        if e_max is None:
+            e_max = int(self.n_rel().max().item()) if self.B else 0
+        e_max = int(e_max)
+        if not self.row_ptr.is_cuda:
+            return self._to_dense_host(dtype, e_max)
+        Rr = torch.empty((self.B, e_max, self.N), dtype=torch.float32, device=dev)
+        Rs = torch.empty((self.B, e_max, self.N), dtype=torch.float32, device=dev)
+        if Rr.numel() == 0:
+            self.overflow = (self.row_ptr[-1:] > 0).to(torch.int32)
+            return Rr.to(dtype), Rs.to(dtype)
+        self.overflow = torch.empty(1, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _lib.lib().ag_edges_to_dense(self.row_ptr.data_ptr(), self.edge_recv.data_ptr(), self.edge_send.data_ptr(), self.B, self.N,
+                                              e_max, Rr.data_ptr(), Rs.data_ptr(), self.overflow.data_ptr(), _stream_ptr(dev))
+        _lib.check(rc, "ag_edges_to_dense")
+        return Rr.to(dtype), Rs.to(dtype)
+
+    def _to_dense_host(self, dtype, e_max):
+        """to_dense of an adjacency held in host memory (csr_from_dense of CPU tensors): the same tensors by torch indexing."""
+        n = self.n_rel()
+        self.overflow = (n > e_max).any().to(torch.int32).reshape(1)
+        Rr = torch.zeros((self.B, e_max, self.N), dtype=dtype)
+        Rs = torch.zeros((self.B, e_max, self.N), dtype=dtype)
+        total = int(self.row_ptr[-1].item())
+        if total and e_max:
             r = self.edge_recv[:total].long()
             s = self.edge_send[:total].long()
             b = r // self.N
-            start = self.row_ptr.long()[b * self.N]
-            idx = torch.arange(total, device=dev) - start
+            idx = torch.arange(total) - self.row_ptr.long()[b * self.N]
+            keep = idx < e_max
+            b, idx, r, s = b[keep], idx[keep], r[keep], s[keep]
             Rr[b, idx, r - b * self.N] = 1
             Rs[b, idx, s - b * self.N] = 1
         return Rr, Rs
@@ -134,20 +159,23 @@ def build_edges(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=
     return CSREdges(row_ptr, edge_recv, edge_send, B, N, e_cap)
 
 
-def construct_edges_from_states(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=False):
-    """Drop-in for graph.py:38-89: states (N,3) -> (Rr, Rs) of shape (n_rel, N)."""
-    n_tools = int(tool_mask.sum().item())
+def construct_edges_from_states(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=False, max_tools=None, max_nR=None):
+    """Drop-in for graph.py:38-89: states (N,3) -> (Rr, Rs) of shape (n_rel, N).
+    Two optional bounds make the call free of host reads (safe to capture): `max_tools` >= the number of tool slots (else counted, one
+    read) and `max_nR`, the row count to pad to (else n_rel, one read) — see CSREdges.to_dense."""
+    n_tools = int(tool_mask.sum().item()) if max_tools is None else int(max_tools)
     csr = build_edges(states[None], adj_thresh, mask[None], tool_mask[None], topk, connect_tools_all, "single",
                       max_tools=n_tools)
-    Rr, Rs = csr.to_dense(states.dtype)
+    Rr, Rs = csr.to_dense(states.dtype, e_max=max_nR)
     return Rr[0], Rs[0]
 
 
-def construct_edges_from_states_batch(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=False):
-    """Drop-in for graph.py:91-156: states (B,N,3) -> (Rr, Rs) of shape (B, max n_rel, N)."""
-    n_tools = int(tool_mask.sum(1).max().item())
+def construct_edges_from_states_batch(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=False, max_tools=None, max_nR=None):
+    """Drop-in for graph.py:91-156: states (B,N,3) -> (Rr, Rs) of shape (B, max n_rel, N); `max_tools` / `max_nR` as in
+    construct_edges_from_states (with `max_nR` the shape is (B, max_nR, N): the reference's pad_torch(Rr, max_nR) included)."""
+    n_tools = int(tool_mask.sum(1).max().item()) if max_tools is None else int(max_tools)
     csr = build_edges(states, adj_thresh, mask, tool_mask, topk, connect_tools_all, "batch", max_tools=n_tools)
-    return csr.to_dense(states.dtype)
+    return csr.to_dense(states.dtype, e_max=max_nR)
 
 
 def csr_from_dense(Rr, Rs):
@@ -169,3 +197,38 @@ def csr_from_dense(Rr, Rs):
     return CSREdges(row_ptr, recv.int().contiguous() if total else torch.zeros(1, dtype=torch.int32, device=dev),
                     send.int().contiguous() if total else torch.zeros(1, dtype=torch.int32, device=dev), B, N,
                     max(total, 1) if total else 0)
+
+
+def csr_from_dense_device(Rr, Rs):
+    """csr_from_dense for CUDA fp32 pairs as HIP kernels (ag_edges_from_dense, csrc/ag_dense.hip): the same row_ptr / edge_recv /
+    edge_send in every bit, with no host read (safe to capture).  The edge count stays on the device, so e_cap is the bound B*E."""
+    _require_gpu(Rr, "Rr")
+    _require_gpu(Rs, "Rs")
+    if Rr.dtype != torch.float32 or Rs.dtype != torch.float32:
+        raise TypeError(f"csr_from_dense_device reads float32 (got {Rr.dtype}, {Rs.dtype}); csr_from_dense takes any dtype")
+    assert Rr.shape == Rs.shape and Rr.dim() == 3, f"Rr {tuple(Rr.shape)} / Rs {tuple(Rs.shape)}"
+    assert Rr.device == Rs.device, f"Rr on {Rr.device}, Rs on {Rs.device}"
+    B, E, N = Rr.shape
+    dev = Rr.device
+    row_ptr = torch.empty(B * N + 1, dtype=torch.int32, device=dev)
+    edge_recv = torch.empty(max(B * E, 1), dtype=torch.int32, device=dev)
+    edge_send = torch.empty(max(B * E, 1), dtype=torch.int32, device=dev)
+    if B * E * N == 0:
+        return CSREdges(row_ptr.zero_(), edge_recv.zero_(), edge_send.zero_(), B, N, 0)
+    Rr, Rs = Rr.contiguous(), Rs.contiguous()
+    L = _lib.lib()
+    ws = workspace(dev, L.ag_dense_edges_workspace_bytes(B, E, N))
+    with torch.cuda.device(dev):
+        rc = L.ag_edges_from_dense(Rr.data_ptr(), Rs.data_ptr(), B, E, N, row_ptr.data_ptr(), edge_recv.data_ptr(), edge_send.data_ptr(),
+                                   ws.data_ptr(), ws.numel(), _stream_ptr(dev))
+    _lib.check(rc, "ag_edges_from_dense")
+    return CSREdges(row_ptr, edge_recv, edge_send, B, N, B * E)
+
+
+def as_csr(Rr, Rs):
+    """The adjacency of a forward call: a CSREdges as it is, a CUDA fp32 one-hot pair through the kernels, anything else through the host function."""
+    if isinstance(Rr, CSREdges):
+        return Rr
+    if Rr.is_cuda and Rs.device == Rr.device and Rr.dtype == torch.float32 and Rs.dtype == torch.float32:
+        return csr_from_dense_device(Rr, Rs)
+    return csr_from_dense(Rr, Rs)

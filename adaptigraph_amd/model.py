@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .graph import CSREdges, csr_from_dense, workspace, _stream_ptr, _require_gpu
+from .graph import as_csr, workspace, _stream_ptr, _require_gpu
 
 STATE_DICT_KEYS = (
     [f"particle_encoder.model.{i}.{p}" for i in (0, 2, 4) for p in ("weight", "bias")]
@@ -167,7 +167,7 @@ class DynamicsPredictor(nn.Module):
         assert phys.shape == (B, self.material_dim)
         assert action is not None                                                  # model.py:193-194
         assert state.shape == (B, self.n_his, N, 3)
-        edges = Rr if isinstance(Rr, CSREdges) else csr_from_dense(Rr, Rs)
+        edges = as_csr(Rr, Rs)
         assert edges.B == B and edges.N == N
 
         state = state.contiguous().float()

@@ -16,7 +16,7 @@ original `relation_propagator.linear.weight` through its three slices.
 import torch
 import torch.nn.functional as F
 
-from .graph import CSREdges, csr_from_dense
+from .graph import as_csr
 from .model import DynamicsPredictor
 from .train_ops import EdgeViews, add3_relu, edge_inputs, fused_chain, gather_receivers, gather_senders, linear, linear2, message_sum, reset_pending
 
@@ -39,7 +39,7 @@ class TrainableDynamicsPredictor(DynamicsPredictor):
         phys = kwargs[physics_keys[0]].to(dev, torch.float32)
         views = kwargs.get("edge_views")
         if views is None:
-            views = EdgeViews(Rr if isinstance(Rr, CSREdges) else csr_from_dense(Rr, Rs))
+            views = EdgeViews(as_csr(Rr, Rs))
         M, nf = B * N, self.nf_effect
 
         # node inputs [attrs | physics (object slots only) | action], 12-vector [v0, v1, v2, x_cur] per node  (:155-195)
@@ -102,7 +102,7 @@ def unrolled_loss(model, data, n_future, loss_funcs=None):
     data = dict(data)
     if "edge_views" not in data:
         Rr, Rs = data["Rr"], data.get("Rs")
-        data["edge_views"] = EdgeViews(Rr if isinstance(Rr, CSREdges) else csr_from_dense(Rr, Rs))
+        data["edge_views"] = EdgeViews(as_csr(Rr, Rs))
     loss_sum = 0
     for fi in range(n_future):
         gt_state = data["state_future"][:, fi]

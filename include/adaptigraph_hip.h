@@ -143,6 +143,27 @@ int ag_build_edges(const float *pos, const uint8_t *mask, const uint8_t *tool_ma
                    int32_t *edge_recv, int32_t *edge_send, int64_t e_cap, void *workspace, size_t workspace_bytes,
                    ag_stream_t stream);
 
+/* ---- the reference's dense relation matrices <-> the CSR adjacency, on the device, with no host synchronisation (safe to capture).
+ *
+ * ag_edges_from_dense: the input contract of DynamicsPredictor.forward (src/dynamics/model.py:129-160): Rr, Rs (B,E,N) fp32 one-hot, all-zero rows
+ *   = padding (pad_torch / truncate_graph).  Row (b,e) is an edge iff Rr[b,e,:] and Rs[b,e,:] both hold a non-zero entry (a NaN counts as
+ *   non-zero); its receiver / sender is the LOWEST index of one — for 0/1 entries what sum(-1) > 0 and argmax(-1) give, multi-hot rows
+ *   included.  Other values are outside the contract but never lead to an out-of-range index (indices are positions, not values).
+ *   Out, in the layout of ag_build_edges: row_ptr (B*N+1), row_ptr[B*N] = number of edges (stays on the device); edge_recv / edge_send of
+ *   capacity B*E, GLOBAL node ids, sorted by receiver and STABLY: within one receiver in ascending e (the order the segment reduce adds in).
+ *   Rr, Rs need 4-byte alignment only.  B*N and B*E must stay below 2^31.
+ * ag_edges_to_dense: the outputs of construct_edges_from_states_batch (src/dynamics/dataset/graph.py:146-155), padded to E_out rows as
+ *   pad_torch(Rr, max_nR) pads them (src/dynamics/utils.py): row e - row_ptr[b*N] of sample b is one-hot at edge_recv[e] - b*N (Rr) and
+ *   edge_send[e] - b*N (Rs).  Rr, Rs (B,E_out,N) fp32 are written completely, zeros included.  A sample with more than E_out edges
+ *   sets *overflow (device word) to 1 and its surplus edges are dropped; otherwise *overflow is set to 0.  Node ids read from the arrays are
+ *   range-checked (an id outside its sample leaves the row zero); edge_recv / edge_send must hold row_ptr[B*N] entries. */
+size_t ag_dense_edges_workspace_bytes(int B, int E, int N);
+int ag_edges_from_dense(const float *Rr, const float *Rs, int B, int E, int N,
+                        int32_t *row_ptr, int32_t *edge_recv, int32_t *edge_send /* capacity B*E */,
+                        void *workspace, size_t workspace_bytes, ag_stream_t stream);
+int ag_edges_to_dense(const int32_t *row_ptr, const int32_t *edge_recv, const int32_t *edge_send,
+                      int B, int N, int E_out, float *Rr, float *Rs, int32_t *overflow, ag_stream_t stream);
+
 /* Scratch sizes.  ag_*_workspace_bytes(...) holds for ANY model / option setting (per-edge table sized as fp32 rows);
  * ag_*_workspace_bytes_for(m, ...) is exact for model `m` as configured NOW — in precision mode 2 the per-edge table is 16-bit (q16) rows,
  * half the largest buffer: query right before the call (a call checks its own carving against workspace_bytes and fails with AG_ERR_WS,
