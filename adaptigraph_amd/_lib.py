@@ -17,7 +17,8 @@ EXPORTS = ("ag_last_error", "ag_version", "ag_model_create", "ag_model_update_we
            "ag_message_forward", "ag_message_backward", "ag_model_status", "ag_train_pack", "ag_train_chain", "ag_train_weight_grads", "ag_train_weight_grads_workspace_bytes", "ag_add3_relu", "ag_relu_mask", "ag_train_weight_grads_into", "ag_edge_inputs_forward", "ag_edge_inputs_backward",
            "ag_forward_workspace_bytes_for", "ag_rollout_workspace_bytes_for", "ag_rollout_streams_for", "ag_get_option",
            "ag_chamfer_fwd_idx", "ag_chamfer_backward", "ag_fps", "ag_fps_workspace_bytes", "ag_gather_clouds", "ag_assemble_batch",
-           "ag_dense_edges_workspace_bytes", "ag_edges_from_dense", "ag_edges_to_dense")
+           "ag_dense_edges_workspace_bytes", "ag_edges_from_dense", "ag_edges_to_dense",
+           "ag_chamfer_tile_sizes", "ag_chamfer_tiled_workspace_bytes", "ag_chamfer_tiled", "ag_chamfer_tiled_backward")
 KERNEL_CLASSES = ("build_edges", "node_encode", "edge_encode", "aggregate", "node_update", "rollout_step")
 
 AG_VARIANT_SINGLE, AG_VARIANT_BATCH = 0, 1
@@ -128,6 +129,14 @@ def lib():
     L.ag_chamfer_fwd_idx.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4
     L.ag_chamfer_backward.restype = c_int
     L.ag_chamfer_backward.argtypes = [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3
+    L.ag_chamfer_tile_sizes.restype = None
+    L.ag_chamfer_tile_sizes.argtypes = [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
+    L.ag_chamfer_tiled_workspace_bytes.restype = c_size_t
+    L.ag_chamfer_tiled_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    L.ag_chamfer_tiled.restype = c_int
+    L.ag_chamfer_tiled.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
+    L.ag_chamfer_tiled_backward.restype = c_int
+    L.ag_chamfer_tiled_backward.argtypes = [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3
     L.ag_fps_workspace_bytes.restype = c_size_t
     L.ag_fps_workspace_bytes.argtypes = [c_int, c_int]
     L.ag_fps.restype = c_int

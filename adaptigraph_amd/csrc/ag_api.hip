@@ -701,6 +701,61 @@ int ag_chamfer_backward(const float *x, const uint8_t *x_mask, const float *y, c
     return AG_OK;
 }
 
+// ---- the tiled chamfer: clouds of any size up to 2^24 points a side (the valid counts are float adds of 1, exact up to there) ----
+static const int kChamMaxPoints = 1 << 24;
+
+void ag_chamfer_tile_sizes(int *query_tile, int *other_chunk)
+{
+    if (query_tile) *query_tile = kChamTQ;
+    if (other_chunk) *other_chunk = kChamTO;
+}
+
+// near: one float per point of both clouds of every sample
+size_t ag_chamfer_tiled_workspace_bytes(int B, int N, int M)
+{
+    if (B < 1 || N < 1 || M < 1 || N > kChamMaxPoints || M > kChamMaxPoints) return 0;
+    return align_up((size_t)B * ((size_t)N + (size_t)M) * sizeof(float), 256);
+}
+
+static int chamfer_tiled_sizes(const char *who, int B, int N, int M)
+{
+    if (B < 1 || N < 1 || M < 1) return fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (N > kChamMaxPoints || M > kChamMaxPoints) return fail(AG_ERR_ARG, "%s: N=%d M=%d exceed %d points a side", who, N, M, kChamMaxPoints);
+    return AG_OK;
+}
+
+int ag_chamfer_tiled(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched, float *out,
+                     int32_t *idx_x, int32_t *idx_y, void *ws, size_t ws_bytes, ag_stream_t stream)
+{
+    const char *who = "ag_chamfer_tiled";
+    if (!x || !y || !out) return fail(AG_ERR_ARG, "%s: null argument", who);
+    if ((x_mask == nullptr) != (y_mask == nullptr)) return fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    if ((idx_x == nullptr) != (idx_y == nullptr)) return fail(AG_ERR_ARG, "%s: give both index outputs or neither", who);
+    if (int rc = chamfer_tiled_sizes(who, B, N, M)) return rc;
+    const size_t need = ag_chamfer_tiled_workspace_bytes(B, N, M);
+    if (!ws || ws_bytes < need) return fail(AG_ERR_WS, "%s: workspace %zu < %zu bytes", who, ws ? ws_bytes : (size_t)0, need);
+    float *near = static_cast<float *>(ws);
+    if (ag_launch_chamfer_tiled(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, idx_x, idx_y, near, static_cast<hipStream_t>(stream)) != 0)
+        return fail(AG_ERR_ARG, "%s: B=%d samples of %d + %d points need more workgroups than one launch holds", who, B, N, M);
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x,
+                              const int32_t *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy,
+                              ag_stream_t stream)
+{
+    const char *who = "ag_chamfer_tiled_backward";
+    if (!x || !y || !idx_x || !idx_y || !grad_out || !gx) return fail(AG_ERR_ARG, "%s: null argument", who);
+    if ((x_mask == nullptr) != (y_mask == nullptr)) return fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    if (int rc = chamfer_tiled_sizes(who, B, N, M)) return rc;
+    if (ag_launch_chamfer_tiled_backward(x, x_mask, y, y_mask, idx_x, idx_y, grad_out, B, N, M, y_batched ? 1 : 0, gx, gy,
+                                         static_cast<hipStream_t>(stream)) != 0)
+        return fail(AG_ERR_ARG, "%s: B=%d samples of %d + %d points need more workgroups than one launch holds", who, B, N, M);
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 // kept distances of the streaming form: one float per point of every cloud (asked of every call, so that the caller's buffer never depends on which
 // form the library picks for a size)
 size_t ag_fps_workspace_bytes(int B, int N)

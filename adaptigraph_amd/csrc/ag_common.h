@@ -571,3 +571,12 @@ int ag_launch_chamfer_idx(const float *x, const float *y, const unsigned char *x
                           int y_batched, float *out, int *idx_x, int *idx_y, hipStream_t s);
 int ag_launch_chamfer_backward(const float *x, const unsigned char *xmask, const float *y, const unsigned char *ymask, const int *idx_x,
                                const int *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy, hipStream_t s);
+// the tiled chamfer (ag_cost_tiled.hip): a query tile of kChamTQ points per workgroup, the other cloud in LDS chunks of kChamTO points
+// (24 KB of planes per chunk: six workgroups per CU; (kChamTQ + 1) + (2 kChamTO + 1) <= 12 800, so shapes that cross a tile and two chunk
+// boundaries still fit the resident kernels they are compared with).  near: (B, M + N) floats of the caller's.  -1: the grid would not fit.
+constexpr int kChamTQ = 1024, kChamTO = 2048;
+int ag_launch_chamfer_tiled(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,
+                            int y_batched, float *out, int *idx_x, int *idx_y, float *near, hipStream_t s);
+int ag_launch_chamfer_tiled_backward(const float *x, const unsigned char *xmask, const float *y, const unsigned char *ymask, const int *idx_x,
+                                     const int *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy,
+                                     hipStream_t s);

@@ -8,33 +8,52 @@ import ctypes
 import torch
 
 from . import _lib
-from .graph import _require_gpu, _stream_ptr
+from .graph import _require_gpu, _stream_ptr, workspace
 
 
 def _needs_grad(*ts):
     return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
 
 
+def _chamfer_tiled(x, xm, y, ym, y_batched, idx_x=None, idx_y=None):
+    """`ag_chamfer_tiled`: clouds of any size, a sample split over many workgroups; the value (and the indices, when asked for) are the bits
+    of the resident entry points wherever those apply.  Its scratch is the grow-only workspace of the current stream."""
+    B, N, M = x.shape[0], x.shape[1], y.shape[1]
+    L = _lib.lib()
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    nbytes = L.ag_chamfer_tiled_workspace_bytes(B, N, M)
+    ws = workspace(x.device, nbytes)
+    with torch.cuda.device(x.device):
+        rc = L.ag_chamfer_tiled(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(), ym.data_ptr() if ym is not None else None,
+                                B, N, M, y_batched, out.data_ptr(), idx_x.data_ptr() if idx_x is not None else None,
+                                idx_y.data_ptr() if idx_y is not None else None, ws.data_ptr(), nbytes, _stream_ptr(x.device))
+    _lib.check(rc, "ag_chamfer_tiled")
+    return out
+
+
 class _Chamfer(torch.autograd.Function):
     """chamfer with a backward: `ag_chamfer_fwd_idx` (the same value bits as ag_chamfer / ag_chamfer_masked, plus the nearest-neighbour index
     of every point) and `ag_chamfer_backward` (gather form, no atomics: the gradient is the same bits on every call).  x (B,N,3) and y (B|1,M,3)
     fp32 contiguous on one GPU, xm / ym (B,N) / (B|1,M) u8 or both None.  A broadcast y (B > 1, one cloud) gets the sum of the per-sample
-    gradients in ascending sample order."""
+    gradients in ascending sample order.  tiled: `ag_chamfer_tiled` / `ag_chamfer_tiled_backward` instead (no size limit, the same bits)."""
 
     @staticmethod
-    def forward(ctx, x, y, xm, ym):
+    def forward(ctx, x, y, xm, ym, tiled=False):
         B, N, M = x.shape[0], x.shape[1], y.shape[1]
         y_batched = 1 if (y.shape[0] == B and B > 1) else 0
-        out = torch.empty(B, dtype=torch.float32, device=x.device)
         idx_x = torch.empty((B, N), dtype=torch.int32, device=x.device)
         idx_y = torch.empty((B, M), dtype=torch.int32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().ag_chamfer_fwd_idx(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
-                                               ym.data_ptr() if ym is not None else None, B, N, M, y_batched, out.data_ptr(),
-                                               idx_x.data_ptr(), idx_y.data_ptr(), _stream_ptr(x.device))
-        _lib.check(rc, "ag_chamfer_fwd_idx")
+        if tiled:
+            out = _chamfer_tiled(x, xm, y, ym, y_batched, idx_x, idx_y)
+        else:
+            out = torch.empty(B, dtype=torch.float32, device=x.device)
+            with torch.cuda.device(x.device):
+                rc = _lib.lib().ag_chamfer_fwd_idx(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
+                                                   ym.data_ptr() if ym is not None else None, B, N, M, y_batched, out.data_ptr(),
+                                                   idx_x.data_ptr(), idx_y.data_ptr(), _stream_ptr(x.device))
+            _lib.check(rc, "ag_chamfer_fwd_idx")
         ctx.save_for_backward(x, y, idx_x, idx_y)
-        ctx.masks, ctx.y_batched = (xm, ym), y_batched
+        ctx.masks, ctx.y_batched, ctx.tiled = (xm, ym), y_batched, tiled
         ctx.mark_non_differentiable(idx_x, idx_y)
         return out
 
@@ -47,26 +66,32 @@ class _Chamfer(torch.autograd.Function):
         g = grad_out.contiguous().float()
         gx = torch.empty_like(x)
         gy = torch.empty((B, M, 3), dtype=torch.float32, device=x.device) if want_y else None      # (a broadcast y: per-sample rows, summed into row 0)
+        name = "ag_chamfer_tiled_backward" if ctx.tiled else "ag_chamfer_backward"
         with torch.cuda.device(x.device):
-            rc = _lib.lib().ag_chamfer_backward(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
-                                                ym.data_ptr() if ym is not None else None, idx_x.data_ptr(), idx_y.data_ptr(), g.data_ptr(),
-                                                B, N, M, ctx.y_batched, gx.data_ptr(), gy.data_ptr() if want_y else None, _stream_ptr(x.device))
-        _lib.check(rc, "ag_chamfer_backward")
+            rc = getattr(_lib.lib(), name)(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
+                                           ym.data_ptr() if ym is not None else None, idx_x.data_ptr(), idx_y.data_ptr(), g.data_ptr(),
+                                           B, N, M, ctx.y_batched, gx.data_ptr(), gy.data_ptr() if want_y else None, _stream_ptr(x.device))
+        _lib.check(rc, name)
         if want_y and y.shape[0] != B:
             gy = gy[:1]
-        return gx, gy, None, None
+        return gx, gy, None, None, None
 
 
-def chamfer(x, y):
+def chamfer(x, y, tiled=False):
     """x (B,N,3), y (B or 1,M,3) -> (B,)  mean_m min_n ||x-y|| + mean_n min_m ||x-y||   (losses.py:4-10).
-    Differentiable in x and y when grad mode is on and either requires grad (same value bits either way)."""
+    Differentiable in x and y when grad mode is on and either requires grad (same value bits either way).
+    tiled: the form without the N + M <= 12 800 limit of the default (a goal cloud read from a .pcd file, plan.py:139-146), which also spreads
+    a call of few samples over the whole device; the same bits as the default wherever that applies.  A cost function opts in with
+    `partial(losses.chamfer, y=target, tiled=True)`."""
     _require_gpu(x, "x")
     assert x.dim() == 3 and y.dim() == 3 and x.shape[2] == 3 and y.shape[2] == 3
     assert y.shape[0] in (1, x.shape[0])
     if _needs_grad(x, y):
-        return _Chamfer.apply(x.contiguous().float(), y.to(x.device).contiguous().float(), None, None)
+        return _Chamfer.apply(x.contiguous().float(), y.to(x.device).contiguous().float(), None, None, tiled)
     x = x.contiguous().float()
     y = y.to(x.device).contiguous().float()
+    if tiled:
+        return _chamfer_tiled(x, None, y, None, 1 if (y.shape[0] == x.shape[0] and x.shape[0] > 1) else 0)
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):
         rc = _lib.lib().ag_chamfer(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], y.shape[1],
@@ -75,8 +100,9 @@ def chamfer(x, y):
     return out
 
 
-def mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask):
-    """Per-sample chamfer over the masked-in points of two padded clouds, one launch for the whole batch -> (bsz,) tensor."""
+def mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask, tiled=False):
+    """Per-sample chamfer over the masked-in points of two padded clouds, one launch for the whole batch -> (bsz,) tensor.
+    tiled: as for `chamfer`."""
     _require_gpu(state_pred, "state_pred")
     dev = state_pred.device
     x = state_pred.contiguous().float()
@@ -85,7 +111,9 @@ def mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask
     ym = state_real_mask.to(dev).ne(0).to(torch.uint8).contiguous()
     assert x.dim() == 3 and y.dim() == 3 and y.shape[0] == x.shape[0] and xm.shape == x.shape[:2] and ym.shape == y.shape[:2]
     if _needs_grad(state_pred, state_real):      # (sys-id by gradient: differentiable in both clouds, same value bits)
-        return _Chamfer.apply(x, y, xm, ym)
+        return _Chamfer.apply(x, y, xm, ym, tiled)
+    if tiled:
+        return _chamfer_tiled(x, xm, y, ym, 1)
     out = torch.empty(x.shape[0], dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
         rc = _lib.lib().ag_chamfer_masked(x.data_ptr(), xm.data_ptr(), y.data_ptr(), ym.data_ptr(), x.shape[0], x.shape[1],
@@ -94,10 +122,10 @@ def mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask
     return out
 
 
-def mean_chamfer(state_pred, state_real, state_pred_mask, state_real_mask):
+def mean_chamfer(state_pred, state_real, state_pred_mask, state_real_mask, tiled=False):
     """losses.py:12-24: numpy (bsz,) of chamfer(state_pred[i][mask_i], state_real[i][mask_i]); the reference loops over
     the batch with one `.item()` sync per sample, here it is one kernel and one copy."""
-    return mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask).double().cpu().numpy()
+    return mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask, tiled).double().cpu().numpy()
 
 
 def box_loss(state, target):

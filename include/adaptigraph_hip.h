@@ -239,6 +239,30 @@ int ag_chamfer_fwd_idx(const float *x, const uint8_t *x_mask, const float *y, co
 int ag_chamfer_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x, const int32_t *idx_y,
                         const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy, ag_stream_t stream);
 
+/* ---- chamfer for clouds of any size (src/planning/losses.py:4-10 has no size limit; src/planning/plan.py:139-146 hands it every point of a
+ * goal .pcd file).  The entry points above keep both clouds of a sample in the LDS of one workgroup; these split a sample into query tiles
+ * (one workgroup each) and stream the other cloud through LDS in chunks, so N and M may each be anything from 1 to 2^24 and a call with few
+ * samples still fills the device.  Where both forms apply, every output is bit-identical to the resident form's. ---- */
+
+/* The tile sizes, for callers and tests that want shapes on either side of them: query points per workgroup, points per LDS chunk. */
+void ag_chamfer_tile_sizes(int *query_tile, int *other_chunk);
+
+/* Scratch of ag_chamfer_tiled (one float per point of both clouds of every sample); 0 for sizes the call refuses. */
+size_t ag_chamfer_tiled_workspace_bytes(int B, int N, int M);
+
+/* chamfer(x, y) of src/planning/losses.py:4-10 and the masked form of losses.py:12-24 in one entry point: arguments and results as
+ * ag_chamfer_fwd_idx, except that x_mask / y_mask are both given or both NULL, idx_x / idx_y are both given or both NULL (NULL: the value only),
+ * and 1 <= N, M <= 2^24.  ws: at least ag_chamfer_tiled_workspace_bytes(B, N, M) bytes (AG_ERR_WS otherwise), 4-byte aligned, free for reuse
+ * once the stream has passed the call.  No host synchronisation, no memset: the call can be captured in a HIP graph. */
+int ag_chamfer_tiled(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched, float *out,
+                     int32_t *idx_x, int32_t *idx_y, void *ws, size_t ws_bytes, ag_stream_t stream);
+
+/* Backward of ag_chamfer_tiled (losses.py:4-24 under autograd) with the indices that call wrote: arguments, formulas, the gy buffer of a
+ * broadcast y and the results as ag_chamfer_backward, bit for bit where that applies; 1 <= N, M <= 2^24.  No atomics, no scratch. */
+int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x,
+                              const int32_t *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy,
+                              ag_stream_t stream);
+
 /* ---- farthest-point key-point sampling (SURVEY.md §8f row n3 data side): the two passes of fps() of src/dynamics/dataset/graph.py:8-36 — the
  * first is dgl.geometry.farthest_point_sampler, the second fps_rad_idx of src/dynamics/utils.py:10-24 — and with them the perception step of
  * the closed loop, src/planning/perception.py:266-279.  B clouds in one launch, one workgroup per cloud.
