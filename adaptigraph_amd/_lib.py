@@ -7,25 +7,23 @@ import ctypes
 import os
 import subprocess
 
+# torch (and with it torch's bundled libamdhip64.so.7) is loaded BEFORE the library: device pointers, streams and events are
+# shared with torch, so both must sit on ONE HIP runtime instance; the loader then binds our DT_NEEDED
+# libamdhip64.so.7 to the already-loaded copy.  (Loaded the other way round, torch finds no device.)
+import torch
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("AG_LIB_PATH") or os.path.join(_HERE, "libadaptigraph_hip.so")   # override: kernel A/B builds
 CSRC = os.path.join(_HERE, "csrc")
 
-EXPORTS = ("ag_last_error", "ag_version", "ag_model_create", "ag_model_update_weights", "ag_model_destroy",
-           "ag_edge_capacity", "ag_edges_workspace_bytes", "ag_build_edges", "ag_forward_workspace_bytes",
-           "ag_forward", "ag_rollout_workspace_bytes", "ag_rollout", "ag_profile_enable", "ag_profile_read", "ag_set_option", "ag_chamfer", "ag_chamfer_masked", "ag_gather_rows", "ag_segment_sum",
-           "ag_message_forward", "ag_message_backward", "ag_model_status", "ag_train_pack", "ag_train_chain", "ag_train_weight_grads", "ag_train_weight_grads_workspace_bytes", "ag_add3_relu", "ag_relu_mask", "ag_train_weight_grads_into", "ag_edge_inputs_forward", "ag_edge_inputs_backward",
-           "ag_forward_workspace_bytes_for", "ag_rollout_workspace_bytes_for", "ag_rollout_streams_for", "ag_get_option",
-           "ag_chamfer_fwd_idx", "ag_chamfer_backward", "ag_fps", "ag_fps_workspace_bytes", "ag_gather_clouds", "ag_assemble_batch",
-           "ag_dense_edges_workspace_bytes", "ag_edges_from_dense", "ag_edges_to_dense",
-           "ag_chamfer_tile_sizes", "ag_chamfer_tiled_workspace_bytes", "ag_chamfer_tiled", "ag_chamfer_tiled_backward")
 KERNEL_CLASSES = ("build_edges", "node_encode", "edge_encode", "aggregate", "node_update", "rollout_step")
 
 AG_VARIANT_SINGLE, AG_VARIANT_BATCH = 0, 1
 AG_HEIGHT_MIN, AG_HEIGHT_MASKED_MEAN = 0, 1
 
-c_void_p, c_int, c_int64, c_size_t, c_float = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t,
-                                               ctypes.c_float)
+c_void_p, c_char_p, c_int, c_int32, c_int64, c_size_t, c_float, c_double, P = (
+    ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double,
+    ctypes.POINTER)
 
 
 class ModelConfig(ctypes.Structure):
@@ -49,6 +47,76 @@ class RolloutParams(ctypes.Structure):
                 ("n_steps", ctypes.c_int32), ("height_mode", ctypes.c_int32), ("gripper_raise", ctypes.c_float)]
 
 
+# The C ABI, one row per export in the order and the groups of include/adaptigraph_hip.h: name -> (restype, [argtypes]).
+# Device pointers, model handles and streams are c_void_p; HOST arrays and structs are typed pointers.
+# tests/test_abi.py holds every row to the header's prototype, position by position.
+SIGNATURES = {
+    "ag_last_error": (c_char_p, []),
+    "ag_version": (c_int, []),
+    # model
+    "ag_model_create": (c_int, [P(ModelConfig), P(c_void_p), P(c_void_p)]),
+    "ag_model_update_weights": (c_int, [c_void_p, P(c_void_p)]),
+    "ag_model_destroy": (c_int, [c_void_p]),
+    "ag_set_option": (c_int, [c_void_p, c_char_p, c_int]),
+    "ag_get_option": (c_int, [c_void_p, c_char_p, P(c_int)]),
+    "ag_model_status": (c_int, [c_void_p, P(c_int), c_void_p]),
+    # edges
+    "ag_edge_capacity": (c_int64, [c_int] * 5),
+    "ag_edges_workspace_bytes": (c_size_t, [c_int] * 5),
+    "ag_build_edges": (c_int, [c_void_p] * 4 + [c_int] * 6 + [c_void_p] * 3 + [c_int64, c_void_p, c_size_t, c_void_p]),
+    # dense Rr / Rs <-> CSR
+    "ag_dense_edges_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ag_edges_from_dense": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "ag_edges_to_dense": (c_int, [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 4),
+    # forward
+    "ag_forward_workspace_bytes": (c_size_t, [c_int, c_int, c_int64]),
+    "ag_forward_workspace_bytes_for": (c_size_t, [c_void_p, c_int, c_int, c_int64]),
+    "ag_forward": (c_int, [c_void_p] * 5 + [c_int] + [c_void_p] * 4 + [c_int64] + [c_int] * 3 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    # rollout
+    "ag_rollout_workspace_bytes": (c_size_t, [P(RolloutParams)]),
+    "ag_rollout_workspace_bytes_for": (c_size_t, [c_void_p, P(RolloutParams)]),
+    "ag_rollout_streams_for": (c_int, [c_void_p, P(RolloutParams)]),
+    "ag_rollout": (c_int, [c_void_p, P(RolloutParams)] + [c_void_p] * 13 + [c_size_t, c_void_p]),
+    # chamfer, both clouds resident in LDS
+    "ag_chamfer": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2),
+    "ag_chamfer_masked": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2),
+    "ag_chamfer_fwd_idx": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4),
+    "ag_chamfer_backward": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3),
+    # chamfer, tiled: clouds of any size
+    "ag_chamfer_tile_sizes": (None, [P(c_int), P(c_int)]),
+    "ag_chamfer_tiled_workspace_bytes": (c_size_t, [c_int] * 3),
+    "ag_chamfer_tiled": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "ag_chamfer_tiled_backward": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3),
+    # farthest-point sampling
+    "ag_fps_workspace_bytes": (c_size_t, [c_int] * 2),
+    "ag_fps": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    # training batches assembled on the device
+    "ag_gather_clouds": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3),
+    "ag_assemble_batch": (c_int, [P(BatchDims)] + [c_void_p] * 8 + [P(BatchOut), c_void_p]),
+    # training path: graph pieces
+    "ag_gather_rows": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p]),
+    "ag_segment_sum": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_void_p]),
+    "ag_message_forward": (c_int, [c_void_p] * 6 + [c_int64, c_int, c_void_p]),
+    "ag_message_backward": (c_int, [c_void_p] * 8 + [c_int64, c_int, c_void_p]),
+    # training path: dense stacks
+    "ag_train_pack": (c_int, [c_void_p] * 2 + [c_int] * 8 + [c_void_p] * 2),
+    "ag_train_chain": (c_int, [c_int] * 3 + [c_void_p] * 2 + [P(c_void_p), c_void_p, P(c_void_p), c_void_p, c_int64, c_int, c_void_p]),
+    "ag_edge_inputs_forward": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 3 + [c_int64, c_void_p]),
+    "ag_edge_inputs_backward": (c_int, [c_void_p] + [c_int] * 3 + [c_void_p] * 9 + [c_int64, c_int64, c_void_p]),
+    "ag_add3_relu": (c_int, [c_void_p] * 4 + [c_int64, c_void_p]),
+    "ag_relu_mask": (c_int, [c_void_p] * 3 + [c_int64, c_void_p]),
+    "ag_train_weight_grads_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "ag_train_weight_grads": (c_int, [c_int, P(c_void_p), P(c_int32), P(c_void_p), P(c_int32), P(c_int32), c_int64, c_void_p, c_void_p, c_size_t,
+                                      c_void_p]),
+    "ag_train_weight_grads_into": (c_int, [c_int, P(c_void_p), P(c_int32), P(c_void_p), P(c_int32), P(c_int32), c_int64, c_void_p,
+                                           P(c_void_p), P(c_int32), P(c_void_p), P(c_int32), c_void_p, c_size_t, c_void_p]),
+    # per-kernel timing
+    "ag_profile_enable": (c_int, [c_void_p, c_int]),
+    "ag_profile_read": (c_int, [c_void_p, P(c_double), P(c_int64), P(c_int64)]),
+}
+EXPORTS = tuple(SIGNATURES)
+
+
 def build(force=False):
     """Compile the HIP library in-tree for gfx950 (hipcc cross-compiles without a GPU)."""
     srcs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hip", ".h")) or f in ("Makefile", "exports.map")]
@@ -70,115 +138,12 @@ def lib():
         raise RuntimeError(
             f"adaptigraph_amd: {LIB_PATH} is missing. The engine has no CPU fallback; build it with "
             "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc, no GPU required).")
-    # Load torch (and with it torch's bundled libamdhip64.so.7) FIRST: device pointers, streams and events are
-    # shared with torch, so both must sit on ONE HIP runtime instance; the loader then binds our DT_NEEDED
-    # libamdhip64.so.7 to the already-loaded copy.  (Loaded the other way round, torch finds no device.)
-    import torch  # noqa: F401
-    L = ctypes.CDLL(LIB_PATH)
-    for name in EXPORTS:
-        if not hasattr(L, name):
+    L = ctypes.CDLL(LIB_PATH)           # (torch is loaded by now: see the import at the top)
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name, None)
+        if fn is None:
             raise RuntimeError(f"adaptigraph_amd: {LIB_PATH} does not export {name} (stale build?)")
-    L.ag_last_error.restype = ctypes.c_char_p
-    L.ag_version.restype = c_int
-    L.ag_model_create.restype = c_int
-    L.ag_model_create.argtypes = [ctypes.POINTER(ModelConfig), ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p)]
-    L.ag_model_update_weights.restype = c_int
-    L.ag_model_update_weights.argtypes = [c_void_p, ctypes.POINTER(c_void_p)]
-    L.ag_model_destroy.restype = c_int
-    L.ag_model_destroy.argtypes = [c_void_p]
-    L.ag_edge_capacity.restype = c_int64
-    L.ag_edge_capacity.argtypes = [c_int] * 5
-    L.ag_edges_workspace_bytes.restype = c_size_t
-    L.ag_edges_workspace_bytes.argtypes = [c_int] * 5
-    L.ag_build_edges.restype = c_int
-    L.ag_build_edges.argtypes = [c_void_p] * 4 + [c_int] * 6 + [c_void_p] * 3 + [c_int64, c_void_p, c_size_t, c_void_p]
-    L.ag_dense_edges_workspace_bytes.restype = c_size_t
-    L.ag_dense_edges_workspace_bytes.argtypes = [c_int] * 3
-    L.ag_edges_from_dense.restype = c_int
-    L.ag_edges_from_dense.argtypes = [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 4 + [c_size_t, c_void_p]
-    L.ag_edges_to_dense.restype = c_int
-    L.ag_edges_to_dense.argtypes = [c_void_p] * 3 + [c_int] * 3 + [c_void_p] * 4
-    L.ag_forward_workspace_bytes.restype = c_size_t
-    L.ag_forward_workspace_bytes.argtypes = [c_int, c_int, c_int64]
-    L.ag_forward_workspace_bytes_for.restype = c_size_t
-    L.ag_forward_workspace_bytes_for.argtypes = [c_void_p, c_int, c_int, c_int64]
-    L.ag_rollout_workspace_bytes_for.restype = c_size_t
-    L.ag_rollout_workspace_bytes_for.argtypes = [c_void_p, ctypes.POINTER(RolloutParams)]
-    L.ag_rollout_streams_for.restype = c_int
-    L.ag_rollout_streams_for.argtypes = [c_void_p, ctypes.POINTER(RolloutParams)]
-    L.ag_forward.restype = c_int
-    L.ag_forward.argtypes = ([c_void_p] * 5 + [c_int] + [c_void_p] * 4 + [c_int64] + [c_int] * 3 + [c_void_p] * 3 +
-                             [c_size_t, c_void_p])
-    L.ag_rollout_workspace_bytes.restype = c_size_t
-    L.ag_rollout_workspace_bytes.argtypes = [ctypes.POINTER(RolloutParams)]
-    L.ag_rollout.restype = c_int
-    L.ag_rollout.argtypes = [c_void_p, ctypes.POINTER(RolloutParams)] + [c_void_p] * 13 + [c_size_t, c_void_p]
-    L.ag_chamfer.restype = c_int
-    L.ag_chamfer.argtypes = [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.ag_gather_rows.restype = c_int
-    L.ag_gather_rows.argtypes = [c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p]
-    L.ag_segment_sum.restype = c_int
-    L.ag_segment_sum.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_int, c_void_p]
-    L.ag_message_forward.restype = c_int
-    L.ag_message_forward.argtypes = [c_void_p] * 6 + [ctypes.c_int64, c_int, c_void_p]
-    L.ag_message_backward.restype = c_int
-    L.ag_message_backward.argtypes = [c_void_p] * 8 + [ctypes.c_int64, c_int, c_void_p]
-    L.ag_chamfer_masked.restype = c_int
-    L.ag_chamfer_masked.argtypes = [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]
-    L.ag_chamfer_fwd_idx.restype = c_int
-    L.ag_chamfer_fwd_idx.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4
-    L.ag_chamfer_backward.restype = c_int
-    L.ag_chamfer_backward.argtypes = [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3
-    L.ag_chamfer_tile_sizes.restype = None
-    L.ag_chamfer_tile_sizes.argtypes = [ctypes.POINTER(c_int), ctypes.POINTER(c_int)]
-    L.ag_chamfer_tiled_workspace_bytes.restype = c_size_t
-    L.ag_chamfer_tiled_workspace_bytes.argtypes = [c_int, c_int, c_int]
-    L.ag_chamfer_tiled.restype = c_int
-    L.ag_chamfer_tiled.argtypes = [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
-    L.ag_chamfer_tiled_backward.restype = c_int
-    L.ag_chamfer_tiled_backward.argtypes = [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3
-    L.ag_fps_workspace_bytes.restype = c_size_t
-    L.ag_fps_workspace_bytes.argtypes = [c_int, c_int]
-    L.ag_fps.restype = c_int
-    L.ag_fps.argtypes = [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]
-    L.ag_gather_clouds.restype = c_int
-    L.ag_gather_clouds.argtypes = [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]
-    L.ag_assemble_batch.restype = c_int
-    L.ag_assemble_batch.argtypes = [ctypes.POINTER(BatchDims)] + [c_void_p] * 8 + [ctypes.POINTER(BatchOut), c_void_p]
-    L.ag_train_pack.restype = c_int
-    L.ag_train_pack.argtypes = [c_void_p, c_void_p] + [c_int] * 8 + [c_void_p, c_void_p]
-    L.ag_train_chain.restype = c_int
-    L.ag_train_chain.argtypes = [c_int, c_int, c_int, c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_void_p, ctypes.POINTER(c_void_p), c_void_p,
-                                 ctypes.c_int64, c_int, c_void_p]
-    L.ag_train_weight_grads_workspace_bytes.restype = c_size_t
-    L.ag_train_weight_grads_workspace_bytes.argtypes = [ctypes.c_int64, c_int]
-    L.ag_train_weight_grads.restype = c_int
-    L.ag_train_weight_grads.argtypes = [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_void_p),
-                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, c_void_p, c_void_p, c_size_t,
-                                        c_void_p]
-    L.ag_train_weight_grads_into.restype = c_int
-    L.ag_train_weight_grads_into.argtypes = [c_int, ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_void_p),
-                                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32), ctypes.c_int64, c_void_p,
-                                             ctypes.POINTER(c_void_p), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(c_void_p),
-                                             ctypes.POINTER(ctypes.c_int32), c_void_p, c_size_t, c_void_p]
-    L.ag_edge_inputs_forward.restype = c_int
-    L.ag_edge_inputs_forward.argtypes = [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, ctypes.c_int64, c_void_p]
-    L.ag_edge_inputs_backward.restype = c_int
-    L.ag_edge_inputs_backward.argtypes = [c_void_p, c_int, c_int, c_int] + [c_void_p] * 9 + [ctypes.c_int64, ctypes.c_int64, c_void_p]
-    L.ag_add3_relu.restype = c_int
-    L.ag_add3_relu.argtypes = [c_void_p] * 4 + [ctypes.c_int64, c_void_p]
-    L.ag_relu_mask.restype = c_int
-    L.ag_relu_mask.argtypes = [c_void_p] * 3 + [ctypes.c_int64, c_void_p]
-    L.ag_model_status.restype = c_int
-    L.ag_model_status.argtypes = [c_void_p, ctypes.POINTER(c_int), c_void_p]
-    L.ag_set_option.restype = c_int
-    L.ag_set_option.argtypes = [c_void_p, ctypes.c_char_p, c_int]
-    L.ag_get_option.restype = c_int
-    L.ag_get_option.argtypes = [c_void_p, ctypes.c_char_p, ctypes.POINTER(c_int)]
-    L.ag_profile_enable.restype = c_int
-    L.ag_profile_enable.argtypes = [c_void_p, c_int]
-    L.ag_profile_read.restype = c_int
-    L.ag_profile_read.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(c_int64), ctypes.POINTER(c_int64)]
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
 
@@ -186,3 +151,63 @@ def lib():
 def check(rc, what):
     if rc != 0:
         raise RuntimeError(f"{what} failed ({rc}): {lib().ag_last_error().decode()}")
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Calling a stream-taking entry point with torch tensors
+# ---------------------------------------------------------------------------------------------------------------------
+def _stream_ptr(device):
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(name, device, *args):
+    """`name(*args, stream)` for an int-returning entry point whose last parameter is the stream: with `device` current, on that device's
+    current stream, every torch.Tensor passed as its data_ptr() and None as a null pointer (ints, ctypes arrays, byref(...) and pointer
+    arithmetic as they are); a non-zero return code raises with the library's message.  Nothing else: no synchronisation, no allocation,
+    no .contiguous() or dtype conversion, which stay with the caller.  `name` may carry a note for the message in parentheses
+    ("ag_train_chain(forward)").  Entry points without a stream are called directly: check(lib().ag_x(...), "ag_x")."""
+    fn = _ENTRY.get(name) or _entry(name)
+    Tensor = torch.Tensor
+    ptrs = [a.data_ptr() if isinstance(a, Tensor) else a for a in args]
+    if device.index == torch.cuda.current_device():      # already current: the context below would set and restore this same device
+        rc = fn(*ptrs, _stream_ptr(device))
+    else:
+        with torch.cuda.device(device):
+            rc = fn(*ptrs, _stream_ptr(device))
+    if rc:
+        check(rc, name)
+
+
+_ENTRY = {}     # name as given to call() -> bound function: the training step is host-bound at several hundred of these calls
+
+
+def _entry(name):
+    fn = _ENTRY[name] = getattr(lib(), name.partition("(")[0])
+    return fn
+
+
+_WS = {}
+
+
+def workspace(device, nbytes):
+    """Grow-only scratch buffer handed to the C ABI (the library never allocates scratch), one per (device, stream):
+    calls enqueued on different streams may overlap, so they must not share scratch."""
+    key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
+    buf = _WS.get(key)
+    if buf is None or buf.numel() < nbytes:
+        buf = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
+        _WS[key] = buf
+    return buf
+
+
+def _require_gpu(t, name):
+    if not t.is_cuda:
+        raise RuntimeError(f"adaptigraph_amd: `{name}` must live on an MI355X (got {t.device}); "
+                           "the engine has no CPU path")
+
+
+def _u8(t, device=None):
+    """A bool / integer mask as the uint8 tensor the kernels read, on `device` when given: a view of the contiguous bool, otherwise a copy."""
+    if t.dtype == torch.bool:
+        return t.to(device=device).contiguous().view(torch.uint8)
+    return t.to(device=device, dtype=torch.uint8).contiguous()

@@ -229,28 +229,25 @@ class DeviceBatcher:
         """Device tables (`upload`) -> the batch, enqueued on the current stream: ag_gather_clouds, both sampling passes, ag_assemble_batch.
         n_max / K: the largest cloud and the largest min(max_nobj, cloud size) of the batch.  No host synchronisation (safe under capture)."""
         from . import _lib
-        from .graph import _stream_ptr
         d = self.dataset
         H, Fu, no, ns, B = d.n_his, d.n_future, d.obj_dim, d.state_dim, int(dev["epi"].shape[0])
-        L, device = _lib.lib(), self.device
+        device = self.device
         f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=device)
         mask = lambda *shape: torch.empty(shape, dtype=torch.bool, device=device)
         pts, count = f32(B, n_max, 3), torch.empty(B, dtype=torch.int32, device=device)
+        _lib.call("ag_gather_clouds", device, self.obj_store, self.episodes, int(self.episodes.shape[0]), dev["epi"], dev["fps_frame"], B, int(n_max),
+                  pts, count)
         with torch.cuda.device(device):
-            _lib.check(L.ag_gather_clouds(self.obj_store.data_ptr(), self.episodes.data_ptr(), int(self.episodes.shape[0]), dev["epi"].data_ptr(),
-                                          dev["fps_frame"].data_ptr(), B, int(n_max), pts.data_ptr(), count.data_ptr(), _stream_ptr(device)),
-                       "ag_gather_clouds")
             picks = two_pass_tensors(pts, count, dev["k1"], dev["start1"], dev["start2"], dev["radius"], int(K)).contiguous()
             out = {"state": f32(B, H, ns, 3), "action": f32(B, ns, 3), "eef_future": f32(B, Fu - 1, ns, 3), "action_future": f32(B, Fu - 1, ns, 3),
                    "state_future": f32(B, Fu, no, 3), "attrs": f32(B, ns, 2), "p_rigid": torch.zeros((B, 1), dtype=torch.float32, device=device),
                    "p_instance": f32(B, no, 1), "obj_mask": mask(B, no), "state_mask": mask(B, ns), "eef_mask": mask(B, ns),
                    "material_index": torch.empty((B, no, self.n_mat), dtype=torch.int64, device=device)}
-            dims = _lib.BatchDims(B, H, Fu, no, ns - no, int(K), self.n_mat, self.mat_col, int(self.episodes.shape[0]), self.tool_f64)
-            ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
-            outs = _lib.BatchOut(*[ptr(out[k]) for k, _ in _lib.BatchOut._fields_])
-            _lib.check(L.ag_assemble_batch(ctypes.byref(dims), self.obj_store.data_ptr(), self.tool_store.data_ptr(), self.episodes.data_ptr(),
-                                           dev["epi"].data_ptr(), dev["frames"].data_ptr(), picks.data_ptr(), ptr(dev.get("noise")),
-                                           ptr(dev.get("rot")), ctypes.byref(outs), _stream_ptr(device)), "ag_assemble_batch")
+        dims = _lib.BatchDims(B, H, Fu, no, ns - no, int(K), self.n_mat, self.mat_col, int(self.episodes.shape[0]), self.tool_f64)
+        ptr = lambda t: t.data_ptr() if t is not None and t.numel() else None
+        outs = _lib.BatchOut(*[ptr(out[k]) for k, _ in _lib.BatchOut._fields_])
+        _lib.call("ag_assemble_batch", device, ctypes.byref(dims), self.obj_store, self.tool_store, self.episodes, dev["epi"], dev["frames"], picks,
+                  ptr(dev.get("noise")), ptr(dev.get("rot")), ctypes.byref(outs))
         for m in d.materials:
             out[m + "_physics_param"] = dev["phys_" + m]
         return out

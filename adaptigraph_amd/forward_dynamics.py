@@ -14,12 +14,9 @@ import os
 import torch
 
 from . import _lib
-from .graph import threshold_sq, workspace, _stream_ptr
+from ._lib import _u8, workspace
+from .graph import threshold_sq
 from .plan_utils import decode_action
-
-
-def _u8(t):
-    return t.contiguous().view(torch.uint8) if t.dtype == torch.bool else t.to(torch.uint8).contiguous()
 
 
 def rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr_sq, repeat, n_steps, topk,
@@ -50,13 +47,8 @@ def rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr_
     obj_u8 = _u8(obj_mask) if obj_mask is not None else None
     repeat = repeat.to(dev, torch.int32).contiguous()
     thr_sq = thr_sq.contiguous()
-    with torch.cuda.device(dev):
-        rc = L.ag_rollout(h, ctypes.byref(prm), state0.data_ptr(), delta.data_ptr(), attrs.data_ptr(),
-                          p_instance.data_ptr(), phys.data_ptr(), mask_u8.data_ptr(), tool_u8.data_ptr(),
-                          obj_u8.data_ptr() if obj_u8 is not None else None, thr_sq.data_ptr(), repeat.data_ptr(),
-                          out_seq.data_ptr(), state_final.data_ptr() if return_state else None, ws.data_ptr(),
-                          ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "ag_rollout")
+    _lib.call("ag_rollout", dev, h, ctypes.byref(prm), state0, delta, attrs, p_instance, phys, mask_u8, tool_u8, obj_u8, thr_sq, repeat,
+              out_seq, state_final, ws, ws.numel())
     return (out_seq, state_final) if return_state else out_seq
 
 

@@ -5,35 +5,11 @@ Drop-in for src/dynamics/dataset/graph.py: `construct_edges_from_states(...)` (:
 one-hot `(Rr, Rs)` return value; `build_edges(...)` is the native fast path returning the CSR
 adjacency the kernels consume (no O(E*N) one-hots, no host sync).
 """
-import ctypes
-
 import numpy as np
 import torch
 
 from . import _lib
-
-_WS = {}
-
-
-def workspace(device, nbytes):
-    """Grow-only scratch buffer handed to the C ABI (the library never allocates scratch), one per (device, stream):
-    calls enqueued on different streams may overlap, so they must not share scratch."""
-    key = (device.type, device.index, torch.cuda.current_stream(device).cuda_stream)
-    buf = _WS.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes * 1.25) + 256, dtype=torch.uint8, device=device)
-        _WS[key] = buf
-    return buf
-
-
-def _stream_ptr(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
-def _require_gpu(t, name):
-    if not t.is_cuda:
-        raise RuntimeError(f"adaptigraph_amd: `{name}` must live on an MI355X (got {t.device}); "
-                           "the engine has no CPU path")
+from ._lib import _WS, _require_gpu, _stream_ptr, _u8, workspace  # noqa: F401  (their home is _lib; tests and older callers reach them here)
 
 
 class CSREdges:
@@ -82,10 +58,7 @@ class CSREdges:
             self.overflow = (self.row_ptr[-1:] > 0).to(torch.int32)
             return Rr.to(dtype), Rs.to(dtype)
         self.overflow = torch.empty(1, dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().ag_edges_to_dense(self.row_ptr.data_ptr(), self.edge_recv.data_ptr(), self.edge_send.data_ptr(), self.B, self.N,
-                                              e_max, Rr.data_ptr(), Rs.data_ptr(), self.overflow.data_ptr(), _stream_ptr(dev))
-        _lib.check(rc, "ag_edges_to_dense")
+        _lib.call("ag_edges_to_dense", dev, self.row_ptr, self.edge_recv, self.edge_send, self.B, self.N, e_max, Rr, Rs, self.overflow)
         return Rr.to(dtype), Rs.to(dtype)
 
     def _to_dense_host(self, dtype, e_max):
@@ -139,8 +112,7 @@ def build_edges(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=
     dev = states.device
     var = _lib.AG_VARIANT_SINGLE if variant == "single" else _lib.AG_VARIANT_BATCH
     states = states.contiguous().float()
-    mask_u8 = mask.to(device=dev).contiguous().view(torch.uint8) if mask.dtype == torch.bool else mask.to(dev, torch.uint8).contiguous()
-    tool_u8 = tool_mask.to(device=dev).contiguous().view(torch.uint8) if tool_mask.dtype == torch.bool else tool_mask.to(dev, torch.uint8).contiguous()
+    mask_u8, tool_u8 = _u8(mask, dev), _u8(tool_mask, dev)
     thr = threshold_sq(adj_thresh, B, dev, var)
     if max_tools is None:
         max_tools = N
@@ -151,11 +123,8 @@ def build_edges(states, adj_thresh, mask, tool_mask, topk=10, connect_tools_all=
     edge_send = torch.empty(max(e_cap, 1), dtype=torch.int32, device=dev)
     nbytes = L.ag_edges_workspace_bytes(B, N, int(topk), connect, int(max_tools))
     ws = workspace(dev, nbytes)
-    with torch.cuda.device(dev):
-        rc = L.ag_build_edges(states.data_ptr(), mask_u8.data_ptr(), tool_u8.data_ptr(), thr.data_ptr(), int(topk),
-                              connect, var, B, N, int(max_tools), row_ptr.data_ptr(), edge_recv.data_ptr(),
-                              edge_send.data_ptr(), e_cap, ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "ag_build_edges")
+    _lib.call("ag_build_edges", dev, states, mask_u8, tool_u8, thr, int(topk), connect, var, B, N, int(max_tools), row_ptr, edge_recv, edge_send,
+              e_cap, ws, ws.numel())
     return CSREdges(row_ptr, edge_recv, edge_send, B, N, e_cap)
 
 
@@ -218,10 +187,7 @@ def csr_from_dense_device(Rr, Rs):
     Rr, Rs = Rr.contiguous(), Rs.contiguous()
     L = _lib.lib()
     ws = workspace(dev, L.ag_dense_edges_workspace_bytes(B, E, N))
-    with torch.cuda.device(dev):
-        rc = L.ag_edges_from_dense(Rr.data_ptr(), Rs.data_ptr(), B, E, N, row_ptr.data_ptr(), edge_recv.data_ptr(), edge_send.data_ptr(),
-                                   ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "ag_edges_from_dense")
+    _lib.call("ag_edges_from_dense", dev, Rr, Rs, B, E, N, row_ptr, edge_recv, edge_send, ws, ws.numel())
     return CSREdges(row_ptr, edge_recv, edge_send, B, N, B * E)
 
 

@@ -3,31 +3,29 @@
 `chamfer` runs the HIP kernel (`ag_chamfer`: no (B,M,N,3) temporaries); the penalties are a few element-wise ops
 over (bsz, n_look_forward, n_obj) and stay as device tensor ops.
 """
-import ctypes
-
 import torch
 
 from . import _lib
-from .graph import _require_gpu, _stream_ptr, workspace
+from ._lib import _require_gpu, workspace
 
 
 def _needs_grad(*ts):
     return torch.is_grad_enabled() and any(t.requires_grad for t in ts)
 
 
+def _y_batched(x, y):
+    """1: one target cloud per sample; 0: one cloud for the whole batch (and a batch of one)."""
+    return 1 if (y.shape[0] == x.shape[0] and x.shape[0] > 1) else 0
+
+
 def _chamfer_tiled(x, xm, y, ym, y_batched, idx_x=None, idx_y=None):
     """`ag_chamfer_tiled`: clouds of any size, a sample split over many workgroups; the value (and the indices, when asked for) are the bits
     of the resident entry points wherever those apply.  Its scratch is the grow-only workspace of the current stream."""
     B, N, M = x.shape[0], x.shape[1], y.shape[1]
-    L = _lib.lib()
     out = torch.empty(B, dtype=torch.float32, device=x.device)
-    nbytes = L.ag_chamfer_tiled_workspace_bytes(B, N, M)
+    nbytes = _lib.lib().ag_chamfer_tiled_workspace_bytes(B, N, M)
     ws = workspace(x.device, nbytes)
-    with torch.cuda.device(x.device):
-        rc = L.ag_chamfer_tiled(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(), ym.data_ptr() if ym is not None else None,
-                                B, N, M, y_batched, out.data_ptr(), idx_x.data_ptr() if idx_x is not None else None,
-                                idx_y.data_ptr() if idx_y is not None else None, ws.data_ptr(), nbytes, _stream_ptr(x.device))
-    _lib.check(rc, "ag_chamfer_tiled")
+    _lib.call("ag_chamfer_tiled", x.device, x, xm, y, ym, B, N, M, y_batched, out, idx_x, idx_y, ws, nbytes)
     return out
 
 
@@ -40,18 +38,14 @@ class _Chamfer(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, y, xm, ym, tiled=False):
         B, N, M = x.shape[0], x.shape[1], y.shape[1]
-        y_batched = 1 if (y.shape[0] == B and B > 1) else 0
+        y_batched = _y_batched(x, y)
         idx_x = torch.empty((B, N), dtype=torch.int32, device=x.device)
         idx_y = torch.empty((B, M), dtype=torch.int32, device=x.device)
         if tiled:
             out = _chamfer_tiled(x, xm, y, ym, y_batched, idx_x, idx_y)
         else:
             out = torch.empty(B, dtype=torch.float32, device=x.device)
-            with torch.cuda.device(x.device):
-                rc = _lib.lib().ag_chamfer_fwd_idx(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
-                                                   ym.data_ptr() if ym is not None else None, B, N, M, y_batched, out.data_ptr(),
-                                                   idx_x.data_ptr(), idx_y.data_ptr(), _stream_ptr(x.device))
-            _lib.check(rc, "ag_chamfer_fwd_idx")
+            _lib.call("ag_chamfer_fwd_idx", x.device, x, xm, y, ym, B, N, M, y_batched, out, idx_x, idx_y)
         ctx.save_for_backward(x, y, idx_x, idx_y)
         ctx.masks, ctx.y_batched, ctx.tiled = (xm, ym), y_batched, tiled
         ctx.mark_non_differentiable(idx_x, idx_y)
@@ -66,12 +60,8 @@ class _Chamfer(torch.autograd.Function):
         g = grad_out.contiguous().float()
         gx = torch.empty_like(x)
         gy = torch.empty((B, M, 3), dtype=torch.float32, device=x.device) if want_y else None      # (a broadcast y: per-sample rows, summed into row 0)
-        name = "ag_chamfer_tiled_backward" if ctx.tiled else "ag_chamfer_backward"
-        with torch.cuda.device(x.device):
-            rc = getattr(_lib.lib(), name)(x.data_ptr(), xm.data_ptr() if xm is not None else None, y.data_ptr(),
-                                           ym.data_ptr() if ym is not None else None, idx_x.data_ptr(), idx_y.data_ptr(), g.data_ptr(),
-                                           B, N, M, ctx.y_batched, gx.data_ptr(), gy.data_ptr() if want_y else None, _stream_ptr(x.device))
-        _lib.check(rc, name)
+        _lib.call("ag_chamfer_tiled_backward" if ctx.tiled else "ag_chamfer_backward", x.device, x, xm, y, ym, idx_x, idx_y, g, B, N, M,
+                  ctx.y_batched, gx, gy)
         if want_y and y.shape[0] != B:
             gy = gy[:1]
         return gx, gy, None, None, None
@@ -91,12 +81,9 @@ def chamfer(x, y, tiled=False):
     x = x.contiguous().float()
     y = y.to(x.device).contiguous().float()
     if tiled:
-        return _chamfer_tiled(x, None, y, None, 1 if (y.shape[0] == x.shape[0] and x.shape[0] > 1) else 0)
+        return _chamfer_tiled(x, None, y, None, _y_batched(x, y))
     out = torch.empty(x.shape[0], dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _lib.lib().ag_chamfer(x.data_ptr(), y.data_ptr(), x.shape[0], x.shape[1], y.shape[1],
-                                   1 if (y.shape[0] == x.shape[0] and x.shape[0] > 1) else 0, out.data_ptr(), _stream_ptr(x.device))
-    _lib.check(rc, "ag_chamfer")
+    _lib.call("ag_chamfer", x.device, x, y, x.shape[0], x.shape[1], y.shape[1], _y_batched(x, y), out)
     return out
 
 
@@ -115,10 +102,7 @@ def mean_chamfer_device(state_pred, state_real, state_pred_mask, state_real_mask
     if tiled:
         return _chamfer_tiled(x, xm, y, ym, 1)
     out = torch.empty(x.shape[0], dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        rc = _lib.lib().ag_chamfer_masked(x.data_ptr(), xm.data_ptr(), y.data_ptr(), ym.data_ptr(), x.shape[0], x.shape[1],
-                                          y.shape[1], 1, out.data_ptr(), _stream_ptr(dev))
-    _lib.check(rc, "ag_chamfer_masked")
+    _lib.call("ag_chamfer_masked", dev, x, xm, y, ym, x.shape[0], x.shape[1], y.shape[1], 1, out)
     return out
 
 

@@ -13,7 +13,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib
-from .graph import as_csr, workspace, _stream_ptr, _require_gpu
+from ._lib import _require_gpu, workspace
+from .graph import as_csr
 
 STATE_DICT_KEYS = (
     [f"particle_encoder.model.{i}.{p}" for i in (0, 2, 4) for p in ("weight", "bias")]
@@ -124,8 +125,7 @@ class DynamicsPredictor(nn.Module):
         occurrence and returns the flag word."""
         dev = torch.device(device if device is not None else self.device)
         flags = ctypes.c_int(0)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.lib().ag_model_status(self.handle(dev), ctypes.byref(flags), _stream_ptr(dev)), "ag_model_status")
+        _lib.call("ag_model_status", dev, self.handle(dev), ctypes.byref(flags))
         if flags.value & 1:
             warnings.warn("adaptigraph_amd: a forward produced non-finite values. If the inputs were finite, an activation of the fp16 "
                           "edge stack of precision mode 2 ('fast') left fp16's range (|x| > 65504): use "
@@ -179,10 +179,6 @@ class DynamicsPredictor(nn.Module):
         L = _lib.lib()
         h = self.handle(dev)
         ws = workspace(dev, L.ag_forward_workspace_bytes_for(h, B, N, edges.e_cap))
-        with torch.cuda.device(dev):
-            rc = L.ag_forward(h, state.data_ptr(), attrs.data_ptr(), action.data_ptr(), p_instance.data_ptr(),
-                              n_inst, phys.data_ptr(), edges.row_ptr.data_ptr(), edges.edge_recv.data_ptr(),
-                              edges.edge_send.data_ptr(), edges.e_cap, B, N, n_p, pred_pos.data_ptr(),
-                              pred_motion.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "ag_forward")
+        _lib.call("ag_forward", dev, h, state, attrs, action, p_instance, n_inst, phys, edges.row_ptr, edges.edge_recv, edges.edge_send,
+                  edges.e_cap, B, N, n_p, pred_pos, pred_motion, ws, ws.numel())
         return pred_pos, pred_motion

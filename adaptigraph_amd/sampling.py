@@ -39,8 +39,7 @@ def fps_device(pts, count, start, K, metric, radius=None):
     once every point is within radius[b] of a pick).  -> (idx (B,K) int32 with -1 past a cloud's last pick, n (B) int32 picks made)."""
     import torch
     from . import _lib
-    from .graph import _require_gpu, _stream_ptr
-    _require_gpu(pts, "pts")
+    _lib._require_gpu(pts, "pts")
     if pts.dtype != torch.float32:
         raise TypeError(f"ag_fps computes in float32; got {pts.dtype} (cast explicitly if rounding the cloud is intended)")
     assert pts.dim() == 3 and pts.shape[2] == 3 and pts.is_contiguous()
@@ -53,11 +52,7 @@ def fps_device(pts, count, start, K, metric, radius=None):
     ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
     idx = torch.empty((B, int(K)), dtype=torch.int32, device=dev)
     n = torch.empty(B, dtype=torch.int32, device=dev)
-    ptr = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(dev):
-        rc = L.ag_fps(pts.data_ptr(), ptr(count), ptr(start), B, N, int(K), int(metric), ptr(radius), idx.data_ptr(), n.data_ptr(),
-                      ws.data_ptr(), ws_bytes, _stream_ptr(dev))
-    _lib.check(rc, "ag_fps")
+    _lib.call("ag_fps", dev, pts, count, start, B, N, int(K), int(metric), radius, idx, n, ws, ws_bytes)
     return idx, n
 
 

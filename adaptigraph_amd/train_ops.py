@@ -11,7 +11,8 @@ import weakref
 import torch
 
 from . import _lib
-from .graph import CSREdges, _require_gpu, _stream_ptr, workspace
+from ._lib import _require_gpu, workspace
+from .graph import CSREdges
 
 
 class EdgeViews:
@@ -32,10 +33,7 @@ class EdgeViews:
 
 def _segment_sum(vals, ptr, perm, n_seg):
     out = torch.empty((n_seg, vals.shape[1]), dtype=torch.float32, device=vals.device)
-    with torch.cuda.device(vals.device):
-        rc = _lib.lib().ag_segment_sum(vals.data_ptr(), ptr.data_ptr(), perm.data_ptr() if perm is not None else None,
-                                       out.data_ptr(), n_seg, vals.shape[1], _stream_ptr(vals.device))
-    _lib.check(rc, "ag_segment_sum")
+    _lib.call("ag_segment_sum", vals.device, vals, ptr, perm, out, n_seg, vals.shape[1])
     return out
 
 
@@ -45,9 +43,7 @@ class _GatherRows(torch.autograd.Function):
         _require_gpu(x, "x")
         x = x.contiguous().float()
         out = torch.empty((idx.shape[0], x.shape[1]), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            rc = _lib.lib().ag_gather_rows(x.data_ptr(), idx.data_ptr(), out.data_ptr(), idx.shape[0], x.shape[1], _stream_ptr(x.device))
-        _lib.check(rc, "ag_gather_rows")
+        _lib.call("ag_gather_rows", x.device, x, idx, out, idx.shape[0], x.shape[1])
         ctx.views = (ptr, perm, x.shape[0])
         return out
 
@@ -63,10 +59,7 @@ class _MessageSum(torch.autograd.Function):
         eterm, hr, hs = eterm.contiguous().float(), hr.contiguous().float(), hs.contiguous().float()
         _require_gpu(hr, "hr")
         agg = torch.empty_like(hr)
-        with torch.cuda.device(hr.device):
-            rc = _lib.lib().ag_message_forward(eterm.data_ptr(), hr.data_ptr(), hs.data_ptr(), views.row_ptr.data_ptr(),
-                                               views.send.data_ptr(), agg.data_ptr(), hr.shape[0], hr.shape[1], _stream_ptr(hr.device))
-        _lib.check(rc, "ag_message_forward")
+        _lib.call("ag_message_forward", hr.device, eterm, hr, hs, views.row_ptr, views.send, agg, hr.shape[0], hr.shape[1])
         ctx.save_for_backward(eterm, hr, hs)
         ctx.views = views
         return agg
@@ -78,11 +71,7 @@ class _MessageSum(torch.autograd.Function):
         grad_agg = grad_agg.contiguous().float()
         g_e = torch.empty_like(eterm)
         g_hr = torch.empty_like(hr)
-        with torch.cuda.device(hr.device):
-            rc = _lib.lib().ag_message_backward(eterm.data_ptr(), hr.data_ptr(), hs.data_ptr(), v.row_ptr.data_ptr(), v.send.data_ptr(),
-                                                grad_agg.data_ptr(), g_e.data_ptr(), g_hr.data_ptr(), hr.shape[0], hr.shape[1],
-                                                _stream_ptr(hr.device))
-        _lib.check(rc, "ag_message_backward")
+        _lib.call("ag_message_backward", hr.device, eterm, hr, hs, v.row_ptr, v.send, grad_agg, g_e, g_hr, hr.shape[0], hr.shape[1])
         g_hs = _segment_sum(g_e, v.col_ptr, v.send_perm, hs.shape[0])
         return g_e, g_hr, g_hs, None
 
@@ -110,10 +99,7 @@ class _EdgeInputs(torch.autograd.Function):
         tab = tab.contiguous().float()
         D = tab.shape[1]
         out = torch.empty((views.E, 2 * attr_dim + 1 + (D - attr_dim - group_dim)), dtype=torch.float32, device=tab.device)
-        with torch.cuda.device(tab.device):
-            rc = _lib.lib().ag_edge_inputs_forward(tab.data_ptr(), D, attr_dim, group_dim, views.recv.data_ptr(), views.send.data_ptr(),
-                                                   out.data_ptr(), views.E, _stream_ptr(tab.device))
-        _lib.check(rc, "ag_edge_inputs_forward")
+        _lib.call("ag_edge_inputs_forward", tab.device, tab, D, attr_dim, group_dim, views.recv, views.send, out, views.E)
         ctx.save_for_backward(tab)
         ctx.meta = (views, attr_dim, group_dim)
         return out
@@ -125,11 +111,8 @@ class _EdgeInputs(torch.autograd.Function):
         g = g.contiguous()
         scratch = torch.empty((2, max(v.E, 1), tab.shape[1]), dtype=torch.float32, device=tab.device)
         gtab = torch.empty_like(tab)
-        with torch.cuda.device(tab.device):
-            rc = _lib.lib().ag_edge_inputs_backward(tab.data_ptr(), tab.shape[1], a, gdim, v.recv.data_ptr(), v.send.data_ptr(), v.row_ptr.data_ptr(),
-                                                    v.col_ptr.data_ptr(), v.send_perm.data_ptr(), g.data_ptr(), scratch[0].data_ptr(),
-                                                    scratch[1].data_ptr(), gtab.data_ptr(), v.E, tab.shape[0], _stream_ptr(tab.device))
-        _lib.check(rc, "ag_edge_inputs_backward")
+        _lib.call("ag_edge_inputs_backward", tab.device, tab, tab.shape[1], a, gdim, v.recv, v.send, v.row_ptr, v.col_ptr, v.send_perm, g,
+                  scratch[0], scratch[1], gtab, v.E, tab.shape[0])
         return gtab, None, None, None
 
 
@@ -172,28 +155,24 @@ def _pack_chain(kind, layers, dev):
     hit = _PACK_CACHE.get((kind, dev.index))
     if hit is not None and hit[0] == key and all(r() is base(x) for r, x in zip(hit[3], (x for Wb in layers for x in Wb))):
         return hit[1], hit[2], prec
-    L = _lib.lib()
     narrow = kind != "decoder"
     n = len(layers)
     fwd = torch.empty(((1 if narrow else 5) + 5 * (n - 1)) * _CHUNK, dtype=torch.float32, device=dev)
     bwd = torch.empty((5 * (n - 1) + (1 if narrow else 5)) * _CHUNK, dtype=torch.float32, device=dev)
-    st = _stream_ptr(dev)
-    with torch.cuda.device(dev):
-        off = 0
-        for l, (W, b) in enumerate(layers):
-            n_out, n_in = W.shape
-            assert W.stride(1) == 1 and b.is_contiguous()
-            compact = narrow and l == 0
-            _lib.check(L.ag_train_pack(W.data_ptr(), b.data_ptr(), n_out, n_in, W.stride(0), 0, 0, int(compact), 1 if compact else 5, prec,
-                                       fwd.data_ptr() + 4 * off, st), "ag_train_pack")
-            off += _CHUNK * (1 if compact else 5)
-        off = 0
-        for l in range(n - 1, -1, -1):
-            W, _ = layers[l]
-            n_out, n_in = W.shape
-            tiles = 1 if (narrow and l == 0) else 5
-            _lib.check(L.ag_train_pack(W.data_ptr(), None, n_in, n_out, W.stride(0), 0, 1, 0, tiles, prec, bwd.data_ptr() + 4 * off, st), "ag_train_pack")
-            off += _CHUNK * tiles
+    off = 0
+    for l, (W, b) in enumerate(layers):
+        n_out, n_in = W.shape
+        assert W.stride(1) == 1 and b.is_contiguous()
+        compact = narrow and l == 0
+        _lib.call("ag_train_pack", dev, W, b, n_out, n_in, W.stride(0), 0, 0, int(compact), 1 if compact else 5, prec, fwd.data_ptr() + 4 * off)
+        off += _CHUNK * (1 if compact else 5)
+    off = 0
+    for l in range(n - 1, -1, -1):
+        W, _ = layers[l]
+        n_out, n_in = W.shape
+        tiles = 1 if (narrow and l == 0) else 5
+        _lib.call("ag_train_pack", dev, W, None, n_in, n_out, W.stride(0), 0, 1, 0, tiles, prec, bwd.data_ptr() + 4 * off)
+        off += _CHUNK * tiles
     _PACK_CACHE[(kind, dev.index)] = (key, fwd, bwd, [weakref.ref(base(x)) for Wb in layers for x in Wb])
     return fwd, bwd, prec
 
@@ -241,10 +220,8 @@ class _FusedChain(torch.autograd.Function):
         else:                                                       # an empty tensor has a null data pointer, which the C ABI refuses
             xin = torch.zeros((1, x.shape[1]), dtype=torch.float32, device=dev)
         ys = [torch.empty((rows_pad, AG_FP), dtype=torch.float32, device=dev) for _ in range(n)]
-        with torch.cuda.device(dev):
-            rc = _lib.lib().ag_train_chain(code, 0, prec, xin.data_ptr(), fwd.data_ptr(), _ptr_array(ys), None, _ptr_array([]), None, rows,
-                                           x.shape[1], _stream_ptr(dev))
-        _lib.check(rc, "ag_train_chain(forward)")
+        # ("(forward)" / "(backward)" below: a note for the error message only, the entry point is ag_train_chain)
+        _lib.call("ag_train_chain(forward)", dev, code, 0, prec, xin, fwd, _ptr_array(ys), None, _ptr_array([]), None, rows, x.shape[1])
         ctx.kind, ctx.rows, ctx.d_in, ctx.bwd, ctx.prec = kind, rows, x.shape[1], bwd, prec
         ctx.params = list(layers) if DIRECT_GRADS else None
         ctx.shapes = [tuple(W.shape) for W, _ in layers]
@@ -261,10 +238,7 @@ class _FusedChain(torch.autograd.Function):
         dy[:rows, : grad_out.shape[1]] = grad_out
         dzs = [torch.empty((rows_pad, AG_FP), dtype=torch.float32, device=dev) for _ in range(n)]
         dx = torch.empty_like(xin)
-        with torch.cuda.device(dev):
-            rc = _lib.lib().ag_train_chain(code, 1, ctx.prec, xin.data_ptr(), ctx.bwd.data_ptr(), _ptr_array(ys), dy.data_ptr(), _ptr_array(dzs),
-                                           dx.data_ptr(), rows, ctx.d_in, _stream_ptr(dev))
-        _lib.check(rc, "ag_train_chain(backward)")
+        _lib.call("ag_train_chain(backward)", dev, code, 1, ctx.prec, xin, ctx.bwd, _ptr_array(ys), dy, _ptr_array(dzs), dx, rows, ctx.d_in)
         if not any(ctx.needs_input_grad[2:]):      # no parameter wants a gradient (a rollout differentiated w.r.t. its inputs only)
             return (None, dx[:rows, : ctx.d_in]) + (None,) * (2 * n)
         # dW_l = dz_l^T y_{l-1}, db_l = column sums of dz_l: all layers in two launches (row-slab split-K on the fp32 MFMA,
@@ -323,10 +297,8 @@ def weight_grads(dzs, prevs, n_ins, rows, params=None):
     i32 = lambda v: (ctypes.c_int32 * 4)(*(list(v) + [0] * (4 - n)))
     if params is None:
         out = torch.empty((n, AG_FP, AG_FP), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = L.ag_train_weight_grads(n, _ptr_array(dzs), i32(t.stride(0) for t in dzs), _ptr_array(prevs), i32(t.stride(0) for t in prevs),
-                                         i32(n_ins), rows, out.data_ptr(), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-        _lib.check(rc, "ag_train_weight_grads")
+        _lib.call("ag_train_weight_grads", dev, n, _ptr_array(dzs), i32(t.stride(0) for t in dzs), _ptr_array(prevs), i32(t.stride(0) for t in prevs),
+                  i32(n_ins), rows, out, ws, ws.numel())
         return out
     keep = [l for l, (W, _) in enumerate(params) if _wants_grad(W)]          # frozen layers (requires_grad False) get no gradient
     if len(keep) < n:
@@ -335,11 +307,9 @@ def weight_grads(dzs, prevs, n_ins, rows, params=None):
         return None
     slots = [(_grad_slot(W), _grad_slot(b)[0] if (b is not None and _wants_grad(b)) else None, W.shape[0]) for W, b in params]
     pv = lambda v: (ctypes.c_void_p * 4)(*(list(v) + [None] * (4 - n)))
-    with torch.cuda.device(dev):
-        rc = L.ag_train_weight_grads_into(n, _ptr_array(dzs), i32(t.stride(0) for t in dzs), _ptr_array(prevs), i32(t.stride(0) for t in prevs),
-                                          i32(n_ins), rows, None, pv(s[0][0] for s in slots), i32(s[0][1] for s in slots), pv(s[1] for s in slots),
-                                          i32(s[2] for s in slots), ws.data_ptr(), ws.numel(), _stream_ptr(dev))
-    _lib.check(rc, "ag_train_weight_grads_into")
+    _lib.call("ag_train_weight_grads_into", dev, n, _ptr_array(dzs), i32(t.stride(0) for t in dzs), _ptr_array(prevs), i32(t.stride(0) for t in prevs),
+              i32(n_ins), rows, None, pv(s[0][0] for s in slots), i32(s[0][1] for s in slots), pv(s[1] for s in slots), i32(s[2] for s in slots),
+              ws, ws.numel())
     return None
 
 
@@ -456,8 +426,7 @@ class _Add3Relu(torch.autograd.Function):
     def forward(ctx, a, b, c):
         a, b, c = a.contiguous(), b.contiguous(), c.contiguous()
         y = torch.empty_like(a)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().ag_add3_relu(a.data_ptr(), b.data_ptr(), c.data_ptr(), y.data_ptr(), a.numel(), _stream_ptr(a.device)), "ag_add3_relu")
+        _lib.call("ag_add3_relu", a.device, a, b, c, y, a.numel())
         ctx.save_for_backward(y)
         return y
 
@@ -466,8 +435,7 @@ class _Add3Relu(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         g = g.contiguous()
         out = torch.empty_like(y)
-        with torch.cuda.device(y.device):
-            _lib.check(_lib.lib().ag_relu_mask(g.data_ptr(), y.data_ptr(), out.data_ptr(), y.numel(), _stream_ptr(y.device)), "ag_relu_mask")
+        _lib.call("ag_relu_mask", y.device, g, y, out, y.numel())
         return out, out, out
 
 

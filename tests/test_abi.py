@@ -17,6 +17,70 @@ def declared_symbols():
     return sorted(set(re.findall(r"\b(ag_[a-z0-9_]+)\s*\(", text)))
 
 
+def declared_prototypes():
+    """name -> (return type, [parameter types]) of every function the header declares, as C text without `const` and parameter names;
+    a pointer parameter of any kind is "*"."""
+    text = open(os.path.join(ROOT, "include", "adaptigraph_hip.h")).read()
+    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)                 # block comments and the inline /*host*/ ones
+    text = re.sub(r"^\s*#.*$", "", text, flags=re.M)                  # preprocessor lines
+    strip = lambda c: " ".join(w for w in c.replace("*", " * ").split() if w != "const")
+    protos = {}
+    for ret, name, params in re.findall(r"([\w\s*]+?)\b(ag_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", text):
+        assert name not in protos, name
+        params = [strip(q) for q in params.split(",")]
+        protos[name] = (strip(ret), [] if params == ["void"] else ["*" if "*" in q else q.rsplit(" ", 1)[0] for q in params])
+    return protos
+
+
+C_VALUE_TYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+                 "ag_stream_t": ctypes.c_void_p}
+C_RETURN_TYPES = dict(C_VALUE_TYPES, **{"char *": ctypes.c_char_p, "void": None})
+
+
+def signature_mismatches(signatures):
+    """Where a name -> (restype, [argtypes]) table disagrees with the header's prototypes; [] when every position agrees."""
+    bad = []
+    protos = declared_prototypes()
+    if sorted(protos) != sorted(signatures):
+        bad.append(f"names differ: {sorted(set(protos) ^ set(signatures))}")
+    for name, (ret, params) in protos.items():
+        restype, argtypes = signatures.get(name, (None, []))
+        if restype is not C_RETURN_TYPES[ret]:
+            bad.append(f"{name}: returns {ret}, table says {restype}")
+        if len(argtypes) != len(params):
+            bad.append(f"{name}: {len(params)} parameters, table has {len(argtypes)}")
+        for i, (c, t) in enumerate(zip(params, argtypes)):
+            if c == "*":
+                ok = t in (ctypes.c_void_p, ctypes.c_char_p) or (isinstance(t, type) and issubclass(t, ctypes._Pointer))
+            else:
+                ok = t is C_VALUE_TYPES[c]
+            if not ok:
+                bad.append(f"{name}: parameter {i} is {'a pointer' if c == '*' else c}, table says {getattr(t, '__name__', t)}")
+    return bad
+
+
+def test_signature_table_matches_the_header_position_by_position():
+    """Every row of _lib.SIGNATURES against its prototype in include/adaptigraph_hip.h: the return type, the number of parameters and every
+    parameter (int / int64_t / size_t / float by their exact ctypes type, ag_stream_t as c_void_p, any pointer as c_void_p, c_char_p or a
+    POINTER type), and the loaded functions carry exactly the table's types.  A wrong count, a pointer where an integer goes (or the
+    reverse) and a 32/64-bit swap are each reported, which the corrupted copies below show."""
+    assert len(declared_prototypes()) == len(declared_symbols()) >= 48
+    assert signature_mismatches(_lib.SIGNATURES) == []
+    L = _lib.lib()
+    for name, (restype, argtypes) in _lib.SIGNATURES.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), name
+    ret, args = _lib.SIGNATURES["ag_fps"]
+    size_at = args.index(ctypes.c_size_t)
+    for row, what in (((ret, args[:-1]), "13 parameters, table has 12"),
+                      ((ret, args[:size_at] + [ctypes.c_void_p] + args[size_at + 1:]), f"parameter {size_at} is size_t, table says c_void_p"),
+                      ((ret, [ctypes.c_size_t] + args[1:]), "parameter 0 is a pointer, table says " + ctypes.c_size_t.__name__),
+                      ((ret, args[:3] + [ctypes.c_int64] + args[4:]), "parameter 3 is int, table says " + ctypes.c_int64.__name__),
+                      ((ctypes.c_int64, args), "returns int, table says")):
+        bad = signature_mismatches(dict(_lib.SIGNATURES, ag_fps=row))
+        assert len(bad) == 1 and bad[0].startswith("ag_fps: " + what), (what, bad)
+
+
 def test_library_exports_every_declared_symbol():
     L = _lib.lib()
     names = declared_symbols()
