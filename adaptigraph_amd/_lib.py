@@ -47,6 +47,10 @@ class RolloutParams(ctypes.Structure):
                 ("n_steps", ctypes.c_int32), ("height_mode", ctypes.c_int32), ("gripper_raise", ctypes.c_float)]
 
 
+class ScriptedParams(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_int32) for n in ("B", "N", "n_p", "n_instance", "topk", "connect_tools_all", "max_tools", "variant", "n_steps")]
+
+
 # The C ABI, one row per export in the order and the groups of include/adaptigraph_hip.h: name -> (restype, [argtypes]).
 # Device pointers, model handles and streams are c_void_p; HOST arrays and structs are typed pointers.
 # tests/test_abi.py holds every row to the header's prototype, position by position.
@@ -77,6 +81,9 @@ SIGNATURES = {
     "ag_rollout_workspace_bytes_for": (c_size_t, [c_void_p, P(RolloutParams)]),
     "ag_rollout_streams_for": (c_int, [c_void_p, P(RolloutParams)]),
     "ag_rollout": (c_int, [c_void_p, P(RolloutParams)] + [c_void_p] * 13 + [c_size_t, c_void_p]),
+    # scripted rollout
+    "ag_rollout_scripted_workspace_bytes_for": (c_size_t, [c_void_p, P(ScriptedParams)]),
+    "ag_rollout_scripted": (c_int, [c_void_p, P(ScriptedParams)] + [c_void_p] * 16 + [c_size_t, c_void_p]),
     # chamfer, both clouds resident in LDS
     "ag_chamfer": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2),
     "ag_chamfer_masked": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2),

@@ -1560,4 +1560,107 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
     return AG_OK;
 }
 
+// ---- scripted rollout (ag_scripted.hip): per step exactly the launches of ag_build_edges + ag_forward, then the scripted state update -------------
+struct ScriptedLayout {
+    AgFwdArgs f{};
+    AgEdgeArgs e{};
+    float *state, *action, *pred_pos, *pred_motion;
+    int64_t e_cap;
+};
+
+static bool scripted_sizes_ok(const ag_scripted_params *p)
+{
+    return p->B >= 1 && p->N >= 1 && p->n_p >= 1 && p->n_p <= p->N && p->n_instance >= 0 && p->topk >= 1 && p->topk <= 64 && p->max_tools >= 0 &&
+           p->n_steps >= 1 && (p->variant == AG_VARIANT_SINGLE || p->variant == AG_VARIANT_BATCH) && (int64_t)p->B * p->N < (1ll << 31) / 64 &&
+           ag_edge_capacity(p->B, p->N, p->topk, p->connect_tools_all, p->max_tools) <= 0x7fffffff;
+}
+
+static void carve_scripted(Carver &c, const ag_scripted_params *p, ScriptedLayout &L, bool eterm16)
+{
+    const size_t rows = (size_t)p->B * p->N;
+    L.e_cap = ag_edge_capacity(p->B, p->N, p->topk, p->connect_tools_all, p->max_tools);
+    L.state = c.take<float>(rows * AG_NHIS * 3);
+    L.action = c.take<float>(rows * 3);
+    L.pred_pos = c.take<float>((size_t)p->B * p->n_p * 3 + 4);
+    L.pred_motion = c.take<float>((size_t)p->B * p->n_p * 3 + 4);
+    AgEdgeArgs &e = L.e;
+    e.row_ptr = c.take<int32_t>(rows + 1);
+    e.edge_recv = c.take<int32_t>((size_t)L.e_cap + 1);
+    e.edge_send = c.take<int32_t>((size_t)L.e_cap + 1);
+    e.B = p->B; e.N = p->N; e.connect = p->connect_tools_all ? 1 : 0;
+    edge_caps(p->N, p->topk, e.connect, p->max_tools, &e.cap0, &e.cap);
+    carve_edges(c, e);
+    carve_forward(c, L.f, p->B, p->N, L.e_cap, eterm16);
+    L.f.e_cap = (int)L.e_cap;
+}
+
+size_t ag_rollout_scripted_workspace_bytes_for(const ag_model *m, const ag_scripted_params *p)
+{
+    if (!p || !scripted_sizes_ok(p)) return 0;
+    Carver c(nullptr, 0);
+    ScriptedLayout L;
+    carve_scripted(c, p, L, resolve_path(m, p->B, p->N, p->n_instance).q16);
+    return align_up(c.off, 256);
+}
+
+int ag_rollout_scripted(ag_model *m, const ag_scripted_params *p, const float *state0, const float *action0, const float *tool_pos,
+                        const float *tool_delta, const float *attrs, const float *p_instance, const float *phys, const uint8_t *mask,
+                        const uint8_t *tool_mask, const float *thr_sq, const float *gt, const uint8_t *obj_mask, float *pred_seq, float *err,
+                        float *state_final, void *workspace, size_t workspace_bytes, ag_stream_t stream)
+{
+    if (!m || !p || !state0 || !action0 || !attrs || !p_instance || !mask || !tool_mask || !thr_sq || !workspace)
+        return fail(AG_ERR_ARG, "ag_rollout_scripted: null argument");
+    if (p->n_steps < 1) return fail(AG_ERR_ARG, "ag_rollout_scripted: n_steps=%d (>= 1)", p->n_steps);
+    if (p->n_p > p->N || p->topk < 1 || p->topk > 64)
+        return fail(AG_ERR_ARG, "ag_rollout_scripted: n_p=%d (<= N=%d) topk=%d (1..64)", p->n_p, p->N, p->topk);
+    if (!scripted_sizes_ok(p))
+        return fail(AG_ERR_ARG, "ag_rollout_scripted: bad sizes B=%d N=%d n_p=%d n_instance=%d max_tools=%d variant=%d", p->B, p->N, p->n_p,
+                    p->n_instance, p->max_tools, p->variant);
+    if ((gt != nullptr) != (err != nullptr)) return fail(AG_ERR_ARG, "ag_rollout_scripted: gt and err are given together or not at all");
+    if (!pred_seq && !err && !state_final) return fail(AG_ERR_ARG, "ag_rollout_scripted: no output: pred_seq, err and state_final are all null");
+    if (p->N > p->n_p && p->n_steps > 1 && (!tool_pos || !tool_delta))
+        return fail(AG_ERR_ARG, "ag_rollout_scripted: null tool script (%d tool slots, %d steps)", p->N - p->n_p, p->n_steps);
+    if (m->cfg.phys_dim > 0 && !phys) return fail(AG_ERR_ARG, "ag_rollout_scripted: phys is null");
+    // the path of an ag_forward call of this batch (one model step per forward: the node inputs change every step, nothing is hoisted)
+    const AgPath path = resolve_path(m, p->B, p->N, p->n_instance);
+    Carver c(workspace, workspace_bytes);
+    ScriptedLayout L;
+    carve_scripted(c, p, L, path.q16);
+    // (against the query's rounded-up figure: a buffer one byte short of what the query asked for is refused, whatever the carving's last offset)
+    if (!c.ok() || workspace_bytes < align_up(c.off, 256))
+        return fail(AG_ERR_WS, "ag_rollout_scripted: workspace %zu < %zu bytes", workspace_bytes, align_up(c.off, 256));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int N = p->N, n_p = p->n_p, T = p->n_steps;
+    const size_t plane = (size_t)N * 3, state_bytes = (size_t)p->B * AG_NHIS * plane * sizeof(float);
+    AG_HIP(hipMemcpyAsync(L.state, state0, state_bytes, hipMemcpyDeviceToDevice, s));
+    AgEdgeArgs &e = L.e;
+    e.mask = mask; e.tool = tool_mask; e.thr_sq = thr_sq; e.topk = p->topk; e.variant = p->variant; e.max_tools = p->max_tools;
+    e.pos = L.state + (size_t)(AG_NHIS - 1) * plane;      // edges on the current frame = state[:, -1]
+    e.pos_stride = (size_t)AG_NHIS * plane;
+    AgFwdArgs &f = L.f;
+    f.state = L.state; f.attrs = attrs; f.p_instance = p_instance; f.phys = phys;
+    f.row_ptr = e.row_ptr; f.edge_recv = e.edge_recv; f.edge_send = e.edge_send;
+    f.pred_pos = L.pred_pos; f.pred_motion = L.pred_motion;
+    f.B = p->B; f.N = N; f.n_p = n_p; f.n_inst = p->n_instance; f.phys_dim = m->cfg.phys_dim;
+    f.pstep = m->cfg.pstep; f.clamp = m->cfg.motion_clamp;
+    setup_args(m, f, path, m->max_blocks);
+    AgScriptArgs st{};
+    st.state = L.state; st.action = L.action; st.pred_pos = L.pred_pos; st.tool_pos = tool_pos; st.tool_delta = tool_delta;
+    st.gt = gt; st.obj_mask = obj_mask; st.pred_seq = pred_seq; st.err = err;
+    st.B = p->B; st.N = N; st.n_p = n_p; st.T = T;
+    for (int t = 0; t < T; ++t) {
+        { Timed tm(m, AG_K_EDGES, s); ag_launch_build_edges(e, s); }
+        f.action = t == 0 ? action0 : L.action;
+        run_node_encode(m, f, s);
+        run_node_encode_fallback(m, f, s);
+        run_edge_encode(m, f, path, s);
+        run_propagate(m, f, path, s);
+        st.t = t;
+        { Timed tm(m, AG_K_ROLLOUT_STEP, s); ag_launch_scripted_step(st, s); }
+    }
+    if (state_final) AG_HIP(hipMemcpyAsync(state_final, L.state, state_bytes, hipMemcpyDeviceToDevice, s));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 }  // extern "C"

@@ -485,6 +485,20 @@ struct AgStepArgs {
 void ag_launch_rollout_step(const AgStepArgs &a, hipStream_t s);
 void ag_launch_zero_words(int32_t *p, int n, hipStream_t s);      // (a kernel, not a memset node: HIP-graph replay)
 
+// Scripted rollout (ag_scripted.hip): the state update behind the forward of step t, tool slots = the last N - n_p of a sample
+struct AgScriptArgs {
+    float *state;                         // (B, AG_NHIS, N, 3) working copy, shifted in place (not by the last step)
+    float *action;                        // (B, N, 3) workspace: the next step's action (not written by the last step)
+    const float *pred_pos;                // (B, n_p, 3)
+    const float *tool_pos, *tool_delta;   // (B, T, N - n_p, 3); entry t + 1 is read, by every step but the last
+    const float *gt;                      // (B, T, n_p, 3) or nullptr
+    const uint8_t *obj_mask;              // (B, n_p) or nullptr: all ones
+    float *pred_seq;                      // (B, T, n_p, 3) or nullptr
+    float *err;                           // (B, T); written when gt is given
+    int B, N, n_p, T, t;
+};
+void ag_launch_scripted_step(const AgScriptArgs &a, hipStream_t s);
+
 // ---- shared-state rollout (ag_shared.hip) ------------------------------------------------------------------------------------
 // dynamics() rolls ONE cloud out under `bsz` sampled pushes (forward_dynamics.py:11-38; 20 000 samples per planning step in config/planning/rope.yaml):
 // wherever a sample's tool has not (yet) had any influence, its particles follow the trajectory of the cloud without a tool — the BASE — bit for bit.

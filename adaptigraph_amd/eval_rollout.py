@@ -14,7 +14,8 @@ import os
 import numpy as np
 import torch
 
-from .graph import build_edges, construct_edges_from_states
+from ._lib import AG_VARIANT_SINGLE
+from .graph import build_edges, construct_edges_from_states, threshold_sq
 from .load import load_dataset, load_positions
 from .sampling import fps, fps_batch
 
@@ -132,10 +133,12 @@ def frame_schedule(pairs, n_his, n_frames, current_start, current_end, next_fn, 
 
 
 @torch.no_grad()
-def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list, obj_pos_list, dataset_config):
+def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list, obj_pos_list, dataset_config, scripted=False):
     """Advance B start graphs together.  graphs[b] from construct_graph, schedules[b] from frame_schedule, eef_pos_list[b]
     (T,N_eef,3) / obj_pos_list[b] (T,N_obj_all,3) the episode the graph came from.  -> [error list per graph]; entry t is
-    the mean key-point distance to the ground truth of frame schedules[b][t][1]."""
+    the mean key-point distance to the ground truth of frame schedules[b][t][1].
+    `scripted`: the step loop as ONE `ag_rollout_scripted` call (forward_dynamics.rollout_scripted) — the same predictions bit for bit, the
+    error reduced by its kernel in a fixed order (equal to the loop's up to the rounding of an fp32 sum), no launch-by-launch host work."""
     P = _dataset_params(dataset_config)
     dev = torch.device(device)
     B, max_nobj = len(graphs), P["max_nobj"]
@@ -157,6 +160,13 @@ def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list,
     phys_key = [k for k in graphs[0] if k.endswith("_physics_param")]
     assert len(phys_key) == 1
     phys = {phys_key[0]: stack(phys_key[0]).reshape(B, -1)}
+    if scripted:
+        from .forward_dynamics import rollout_scripted
+        thr = threshold_sq(P["adj_thresh"], B, dev, AG_VARIANT_SINGLE)
+        errors = rollout_scripted(model, state, action, eef_start, eef_delta, attrs, p_instance, phys[phys_key[0]], state_mask, eef_mask, thr,
+                                  P["topk"], P["connect_tool_all"], n_eef, variant="single", gt=gt, obj_mask=obj_mask,
+                                  return_pred=False)["err"].cpu().numpy()
+        return [[errors[b, t] for t in range(len(schedules[b]))] for b in range(B)]
     n_valid = obj_mask.sum(1).clamp_min(1).float()
     errors = torch.zeros((B, T), device=dev)
     for t in range(T):
@@ -176,12 +186,12 @@ def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list,
 
 def rollout_from_start_graph(graph, fps_idx_list, dataset_config, material_config, model, device, eef_pos, obj_pos,
                              current_start, current_end, get_next_pair_or_break_func, pairs, save_dir=None, viz=False,
-                             imgs=None, cam_info=None):
-    """Reference signature (rollout.py:20-143) for one start graph; `viz` output is not produced by this engine."""
+                             imgs=None, cam_info=None, scripted=False):
+    """Reference signature (rollout.py:20-143) for one start graph; `viz` output is not produced by this engine.  `scripted`: see rollout_batch."""
     n_his = dataset_config["n_his"]
     assert eef_pos.shape[0] == obj_pos.shape[0]
     sched = frame_schedule(pairs, n_his, obj_pos.shape[0], current_start, current_end, get_next_pair_or_break_func)
-    return rollout_batch(model, device, [graph], [fps_idx_list], [sched], [eef_pos], [obj_pos], dataset_config)[0]
+    return rollout_batch(model, device, [graph], [fps_idx_list], [sched], [eef_pos], [obj_pos], dataset_config, scripted=scripted)[0]
 
 
 def _episode_first_pairs(dataset_config, episode_idx):
@@ -207,22 +217,22 @@ def _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_i
 
 
 def rollout_episode_pushes(model, device, dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param,
-                           save_dir, viz=False, imgs=None, cam_info=None, fps_device=None):
+                           save_dir, viz=False, imgs=None, cam_info=None, fps_device=None, scripted=False):
     """-> [error list per push]; writes error_<i>.txt per push like the reference (rollout.py:145-196; no plots/videos)."""
     starts = _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param, device,
                              fps_device=fps_device)
-    errs = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config) if starts else []
+    errs = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config, scripted=scripted) if starts else []
     for i, e in enumerate(errs):
         np.savetxt(os.path.join(save_dir, f"error_{i + 1}.txt"), np.array(e))
     return errs
 
 
-def rollout_dataset(model, device, config, save_dir, viz=False, fps_device=None):
+def rollout_dataset(model, device, config, save_dir, viz=False, fps_device=None, scripted=False):
     """Validation split -> per-episode/per-push error files + error_short.txt (steps x pushes, truncated to the shortest
     rollout), rollout.py:198-265.  All pushes of all episodes run as ONE batch.  -> step_error array.
     `fps_device`: the key-point sampling of EVERY start graph runs there as one `fps_batch` call (one launch per pass for the whole split).
     Building a start graph draws nothing but its sampling's numbers from the RNG, so the draws come in the same order and the start graphs
-    are the same as with the per-graph host sampling."""
+    are the same as with the per-graph host sampling.  `scripted`: see rollout_batch."""
     dataset_config, material_config = config["dataset_config"], config["material_config"]
     pair_lists, physics_params = load_dataset(dataset_config, material_config, phase="valid")
     pair_lists = np.array(pair_lists)
@@ -243,7 +253,7 @@ def rollout_dataset(model, device, config, save_dir, viz=False, fps_device=None)
                               device, fps_idx_lists=fps_idx.get(episode_idx))
         starts.extend(epi)
         owners.extend((episode_idx, i + 1) for i in range(len(epi)))
-    total = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config)
+    total = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config, scripted=scripted)
     for (episode_idx, push), e in zip(owners, total):
         d = os.path.join(save_dir, f"{episode_idx}", "short")
         os.makedirs(d, exist_ok=True)
@@ -269,4 +279,5 @@ def rollout(config, epoch, viz=False):
     model = DynamicsPredictor(config["model_config"], config["material_config"], dataset_config, device)
     model.to(device).eval()
     model.load_state_dict(torch.load(os.path.join(train_config["out_dir"], data_name, "checkpoints", ckpt), map_location=device))
-    return rollout_dataset(model, device, config, save_dir, viz, fps_device=config["rollout_config"].get("fps_device"))
+    return rollout_dataset(model, device, config, save_dir, viz, fps_device=config["rollout_config"].get("fps_device"),
+                           scripted=config["rollout_config"].get("scripted", False))

@@ -52,6 +52,45 @@ def rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr_
     return (out_seq, state_final) if return_state else out_seq
 
 
+def rollout_scripted(model, state0, action0, tool_pos, tool_delta, attrs, p_instance, phys, mask, tool_mask, thr_sq, topk,
+                     connect_tools_all, max_tools, variant="batch", gt=None, obj_mask=None, return_pred=True, return_state=False):
+    """A cloud advanced under a RECORDED tool trajectory in one `ag_rollout_scripted` call (the step loop of src/dynamics/rollout/rollout.py:62-93):
+    per step t the edges of state[:, -1] (builder `variant`), the forward on the current action, then the tool slots placed at tool_pos[:, t+1]
+    and the next action set to tool_delta[:, t+1].  All tensors on the model's GPU; no host synchronisation.
+    state0 (B,H,N,3), action0 (B,N,3) the action of step 0, tool_pos / tool_delta (B,T,N-n_p,3) indexed by step (entry 0 is never read; both may
+    be None without tool slots, T then comes from gt), attrs (B,N,2), p_instance (B,n_p,I), phys (B,P), mask / tool_mask (B,N) bool, thr_sq (B,)
+    rounded as `variant` rounds it (graph.threshold_sq), gt (B,T,n_p,3) ground truth, obj_mask (B,n_p) bool (None: every slot counts).
+    -> dict: "pred_seq" (B,T,n_p,3) every step's prediction (return_pred), "err" (B,T) the masked mean distance to gt (gt given),
+    "state_final" (B,H,N,3) the history the last step's forward read (return_state)."""
+    dev = state0.device
+    B, H, N, _ = state0.shape
+    n_p, n_inst = p_instance.shape[1], p_instance.shape[2]
+    script = tool_pos if tool_pos is not None else gt
+    if script is None:
+        raise ValueError("rollout_scripted: the number of steps comes from tool_pos or gt; both are None")
+    T = script.shape[1]
+    for name, t, shape in (("tool_pos", tool_pos, (B, T, N - n_p, 3)), ("tool_delta", tool_delta, (B, T, N - n_p, 3)), ("gt", gt, (B, T, n_p, 3)),
+                           ("obj_mask", obj_mask, (B, n_p)), ("action0", action0, (B, N, 3))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"rollout_scripted: {name} is {tuple(t.shape)}, expected {shape}")
+    var = _lib.AG_VARIANT_SINGLE if variant == "single" else _lib.AG_VARIANT_BATCH
+    prm = _lib.ScriptedParams(B, N, n_p, n_inst, int(topk), 1 if connect_tools_all else 0, int(max_tools), var, T)
+    f32 = lambda t: None if t is None else t.to(dev, torch.float32).contiguous()      # noqa: E731
+    out = {}
+    if return_pred:
+        out["pred_seq"] = torch.empty((B, T, n_p, 3), dtype=torch.float32, device=dev)
+    if gt is not None:
+        out["err"] = torch.empty((B, T), dtype=torch.float32, device=dev)
+    if return_state:
+        out["state_final"] = torch.empty((B, H, N, 3), dtype=torch.float32, device=dev)
+    h = model.handle(dev)
+    ws = workspace(dev, _lib.lib().ag_rollout_scripted_workspace_bytes_for(h, ctypes.byref(prm)))
+    _lib.call("ag_rollout_scripted", dev, h, ctypes.byref(prm), f32(state0), f32(action0), f32(tool_pos), f32(tool_delta), f32(attrs),
+              f32(p_instance), f32(phys), _u8(mask), _u8(tool_mask), f32(thr_sq), f32(gt), None if obj_mask is None else _u8(obj_mask),
+              out.get("pred_seq"), out.get("err"), out.get("state_final"), ws, ws.numel())
+    return out
+
+
 def _place_tool(task, decoded, theta, y, device):
     """Tool key-points and per-step delta from a decoded action (forward_dynamics.py:42-81 / :237-276)."""
     bsz = decoded.shape[0]

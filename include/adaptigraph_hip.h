@@ -211,6 +211,41 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
                const uint8_t *obj_mask, const float *thr_sq, const int32_t *repeat, float *out_seq,
                float *state_final, void *workspace, size_t workspace_bytes, ag_stream_t stream);
 
+/* ---- scripted rollout: a cloud advanced under a RECORDED tool trajectory, every step's prediction recorded and its mean key-point error
+ * against ground truth reduced on the device.  Replaces the step loop of the evaluation rollout, src/dynamics/rollout/rollout.py:62-93, with
+ * the frame walk of src/dynamics/rollout/graph.py:373-399 resolved by the caller up front (which frames a rollout visits never depends on the
+ * predictions): one call instead of a host round trip per step, no host synchronisation, no allocation, safe to capture — and the script
+ * arrays are read at replay time, so a captured call follows whatever script they hold then.
+ * Per step t = 0 .. T-1 (T = n_steps), on ONE stream: ag_build_edges(variant) on state[:, -1]; ag_forward on the current action; then
+ *   pred_seq[b, t] = pred;   err[b, t] = sum_i obj_mask[b,i] ||pred[b,i] - gt[b,t,i]||_2 / max(sum_i obj_mask[b,i], 1)
+ *   and, unless t = T-1:  state = [state[1:], [pred | tool_pos[b, t+1]]],  action = [0 (object rows) | tool_delta[b, t+1]].
+ * The tool slots are the last N - n_p of a sample and are placed absolutely from the script (rollout.py:84: eef_kp from the recorded frames):
+ * no last + delta, no tool-height rule.  pred_seq and state_final equal, bit for bit, a loop of ag_build_edges + ag_forward calls with the same
+ * model options; the error sum is taken in one fixed order without atomics (two calls give the same bits; a sample without a valid point
+ * gives exactly 0).  "precision" and the kernel-choice options are honoured as ag_forward honours them; "rollout_streams", "cu_split",
+ * "shared_state", "self_edges" and the edge builder's riders belong to ag_rollout and do not apply.
+ * Argument errors and a workspace below the query come back as codes before anything is launched. */
+typedef struct ag_scripted_params {
+    int32_t B, N, n_p, n_instance;
+    int32_t topk, connect_tools_all, max_tools;
+    int32_t variant;      /* AG_VARIANT_SINGLE | AG_VARIANT_BATCH: what ag_build_edges takes */
+    int32_t n_steps;      /* T >= 1 */
+} ag_scripted_params;
+size_t ag_rollout_scripted_workspace_bytes_for(const ag_model *m, const ag_scripted_params *p);
+int ag_rollout_scripted(ag_model *m, const ag_scripted_params *p,
+                        const float *state0,      /* (B, n_his, N, 3) */
+                        const float *action0,     /* (B, N, 3): the action of step 0 */
+                        const float *tool_pos,    /* (B, T, N - n_p, 3): entries t = 1 .. T-1 are read, entry 0 never; NULL if none is read */
+                        const float *tool_delta,  /* same shape, same rule */
+                        const float *attrs, const float *p_instance, const float *phys,
+                        const uint8_t *mask, const uint8_t *tool_mask, const float *thr_sq,
+                        const float *gt,          /* (B, T, n_p, 3) or NULL */
+                        const uint8_t *obj_mask,  /* (B, n_p) or NULL: all ones */
+                        float *pred_seq,          /* (B, T, n_p, 3) or NULL */
+                        float *err,               /* (B, T); given exactly when gt is */
+                        float *state_final,       /* (B, n_his, N, 3) or NULL: the history the last step's forward read */
+                        void *workspace, size_t workspace_bytes, ag_stream_t stream);
+
 /* chamfer(x, y) of src/planning/losses.py:4-10 — the MPPI error term:
  *   x (B,N,3) predicted particles, y (B,M,3) if y_batched else (1,M,3) target cloud  ->  out (B)
  *   out[b] = mean_m min_n ||x[b,n]-y[.,m]|| + mean_n min_m ||x[b,n]-y[.,m]||; N + M <= 12800. */
