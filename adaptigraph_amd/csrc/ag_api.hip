@@ -403,6 +403,73 @@ void edge_caps(int N, int topk, int connect, int max_tools, int *cap0, int *cap)
     *cap = *cap0 + (connect ? max_tools : 0);
 }
 
+struct Lane {   // what a rollout driver keeps per batch part [b0, b0 + B) (the shared-state and the scripted rollout have one part; `st`: ag_rollout's state step)
+    AgFwdArgs f{};
+    AgEdgeArgs e{};
+    AgStepArgs st{};
+    AgPath path{};
+    float *state = nullptr, *pred_pos = nullptr, *pred_motion = nullptr;
+    hipStream_t s = nullptr;
+    int b0 = 0, B = 0;
+};
+
+// One step's buffers of a lane of B samples (Params: ag_rollout_params or ag_scripted_params): predictions of pred_n slots per sample, the lists the edge
+// builder writes and the forward reads (`self_lists`: + the class edges of self-edge elision and its two per-node lists), its scratch, the forward's tables
+template <class Params>
+void carve_step(Carver &c, Lane &l, const Params *p, int B, int pred_n, bool self_lists, bool eterm16, bool full_dedup = false)
+{
+    const int64_t e_cap = ag_edge_capacity(B, p->N, p->topk, p->connect_tools_all, p->max_tools);
+    const size_t rows = (size_t)B * p->N, ecoo = (size_t)e_cap + 1 + (self_lists ? AG_SELF_ROWS : 0);
+    AgEdgeArgs &e = l.e;
+    l.pred_pos = c.take<float>((size_t)B * pred_n * 3 + 4);
+    l.pred_motion = c.take<float>((size_t)B * pred_n * 3 + 4);
+    e.row_ptr = c.take<int32_t>(rows + 1);
+    e.edge_recv = c.take<int32_t>(ecoo);
+    e.edge_send = c.take<int32_t>(ecoo);
+    if (self_lists) {
+        e.self_info = c.take<int32_t>(rows);
+        e.self_pos = c.take<int32_t>(rows);
+    }
+    e.B = B; e.N = p->N; e.connect = p->connect_tools_all ? 1 : 0;
+    edge_caps(p->N, p->topk, e.connect, p->max_tools, &e.cap0, &e.cap);
+    carve_edges(c, e);
+    carve_forward(c, l.f, B, p->N, e_cap, eterm16, full_dedup);
+    l.f.e_cap = (int)e_cap;
+    l.B = B;
+}
+
+// A model step's arguments: the call's tensors and sizes, the model's constants, the edge lists the step reads
+void bind_forward(const ag_model *m, AgFwdArgs &f, int B, int N, int n_p, int n_inst, const float *state, const float *attrs, const float *action,
+                  const float *p_instance, const float *phys, const int32_t *row_ptr, const int32_t *edge_recv, const int32_t *edge_send,
+                  float *pred_pos, float *pred_motion)
+{
+    f.state = state; f.attrs = attrs; f.action = action; f.p_instance = p_instance; f.phys = phys;
+    f.row_ptr = row_ptr; f.edge_recv = edge_recv; f.edge_send = edge_send;
+    f.pred_pos = pred_pos; f.pred_motion = pred_motion;
+    f.B = B; f.N = N; f.n_p = n_p; f.n_inst = n_inst; f.phys_dim = m->cfg.phys_dim;
+    f.pstep = m->cfg.pstep; f.clamp = m->cfg.motion_clamp;
+}
+
+// A rollout lane's edge build: edges on the current frame = the last of the lane's n_his history frames (forward_dynamics.py:125 / :171)
+template <class Params>
+void bind_edges(Lane &l, const Params *p, int variant, int n_his, const uint8_t *mask, const uint8_t *tool_mask, const float *thr_sq)
+{
+    const size_t plane = (size_t)p->N * 3;
+    AgEdgeArgs &e = l.e;
+    e.mask = mask; e.tool = tool_mask; e.thr_sq = thr_sq; e.topk = p->topk; e.variant = variant; e.max_tools = p->max_tools;
+    e.pos = l.state + (size_t)(n_his - 1) * plane; e.pos_stride = (size_t)n_his * plane;
+}
+
+// Rider of the edge builder's launches (AgEdgeArgs): the per-node input rows of the weight-stationary edge encoder.  After setup_args (f.status).
+void wire_tab_rider(Lane &l)
+{
+    if (l.path.edge != AG_EDGE_H3_WS) return;
+    AgEdgeArgs &e = l.e;
+    const AgFwdArgs &f = l.f;
+    e.tab_state = f.state; e.tab_attrs = f.attrs; e.tab_pinst = f.p_instance; e.tab_out = f.edge_node_tab;
+    e.tab_n_inst = f.n_inst; e.tab_n_p = f.n_p; e.tab_status = f.status;
+}
+
 struct Timed {   // RAII: bracket one kernel launch with an event pair when profiling is on
     ag_model *m;
     int k;
@@ -1142,11 +1209,8 @@ int ag_forward(ag_model *m, const float *state, const float *attrs, const float 
     if (B < 1 || N < 1 || n_p < 0 || n_p > N || n_instance < 0 || e_cap < 0 || e_cap > 0x7fffffff)
         return fail(AG_ERR_ARG, "ag_forward: bad sizes B=%d N=%d n_p=%d e_cap=%lld", B, N, n_p, (long long)e_cap);
     AgFwdArgs a{};
-    a.state = state; a.attrs = attrs; a.action = action; a.p_instance = p_instance; a.phys = phys;
-    a.row_ptr = row_ptr; a.edge_recv = edge_recv; a.edge_send = edge_send;
-    a.pred_pos = pred_pos; a.pred_motion = pred_motion;
-    a.B = B; a.N = N; a.n_p = n_p; a.n_inst = n_instance; a.phys_dim = m->cfg.phys_dim; a.e_cap = (int)e_cap;
-    a.pstep = m->cfg.pstep; a.clamp = m->cfg.motion_clamp;
+    bind_forward(m, a, B, N, n_p, n_instance, state, attrs, action, p_instance, phys, row_ptr, edge_recv, edge_send, pred_pos, pred_motion);
+    a.e_cap = (int)e_cap;
     const AgPath path = resolve_path(m, B, N, n_instance);
     Carver c(workspace, workspace_bytes);
     carve_forward(c, a, B, N, e_cap, path.q16);
@@ -1159,26 +1223,6 @@ int ag_forward(ag_model *m, const float *state, const float *attrs, const float 
     run_propagate(m, a, path, s);
     AG_HIP(hipGetLastError());
     return AG_OK;
-}
-
-static void carve_rollout(Carver &c, const ag_rollout_params *p, int B, AgFwdArgs &f, AgEdgeArgs &e, float **state,
-                          float **pred_pos, float **pred_motion, int n_his, bool eterm16)
-{
-    const int64_t e_cap = ag_edge_capacity(B, p->N, p->topk, p->connect_tools_all, p->max_tools);
-    const size_t rows = (size_t)B * p->N;
-    *state = c.take<float>(rows * n_his * 3);
-    *pred_pos = c.take<float>((size_t)B * p->n_p * 3 + 4);
-    *pred_motion = c.take<float>((size_t)B * p->n_p * 3 + 4);
-    e.row_ptr = c.take<int32_t>(rows + 1);
-    e.edge_recv = c.take<int32_t>((size_t)e_cap + 1 + AG_SELF_ROWS);      // (+ the synthetic class edges behind the list: self-edge elision)
-    e.edge_send = c.take<int32_t>((size_t)e_cap + 1 + AG_SELF_ROWS);
-    e.self_info = c.take<int32_t>(rows);
-    e.self_pos = c.take<int32_t>(rows);
-    e.B = B; e.N = p->N; e.connect = p->connect_tools_all ? 1 : 0;
-    edge_caps(p->N, p->topk, e.connect, p->max_tools, &e.cap0, &e.cap);
-    carve_edges(c, e);
-    carve_forward(c, f, B, p->N, e_cap, eterm16);
-    f.e_cap = (int)e_cap;
 }
 
 // The batch is rolled out as up to AG_MAX_PARTS independent parts on separate streams: graphs never interact,
@@ -1200,6 +1244,18 @@ static void part_range(int B, int parts, int k, int *b0, int *nb)
     const int per = (B + parts - 1) / parts;
     *b0 = k * per < B ? k * per : B;
     *nb = (*b0 + per <= B) ? per : B - *b0;
+}
+// The batch parts of an ag_rollout call and of its workspace query: each part's samples, its kernels and its layout, one part behind the other
+static void carve_parts(Carver &c, const ag_model *m, const ag_rollout_params *p, int parts, Lane *lane)
+{
+    for (int k = 0; k < parts; ++k) {
+        Lane &l = lane[k];
+        int B;
+        part_range(p->B, parts, k, &l.b0, &B);
+        l.path = resolve_path(m, B, p->N, p->n_instance, p->n_steps);
+        l.state = c.take<float>((size_t)B * p->N * AG_NHIS * 3);
+        carve_step(c, l, p, B, p->n_p, true, l.path.q16);
+    }
 }
 
 // The two CU-masked streams of the partitioned rollout (created once per cu_split value).  Mask bit b is CU slot b / 8 of XCD b % 8
@@ -1225,13 +1281,6 @@ static int ensure_partition(ag_model *m)
 }
 
 // ---- shared-state rollout (ag_shared.hip): one stream, the batch as ONE part behind the base sample -------------------------------------------------
-struct SharedLayout {
-    AgSharedArgs sh{};
-    AgFwdArgs f{};
-    AgEdgeArgs e{};
-    float *pred_pos = nullptr, *pred_motion = nullptr;
-};
-
 static bool shared_applicable(const ag_model *m, const ag_rollout_params *p)
 {
     if (!m || !p || !m->shared_state || p->B < 2 || p->n_steps < 1) return false;
@@ -1242,13 +1291,12 @@ static bool shared_applicable(const ag_model *m, const ag_rollout_params *p)
     return true;
 }
 
-static void carve_shared(Carver &c, const ag_model *m, const ag_rollout_params *p, SharedLayout &L, bool eterm16)
+static void carve_shared(Carver &c, const ag_model *m, const ag_rollout_params *p, AgSharedArgs &s, Lane &l, bool eterm16)
 {
     const int B1 = p->B + 1, N = p->N, n_p = p->n_p, H = AG_NHIS, Pd = m->cfg.phys_dim, I = p->n_instance;
     const int64_t e_cap = ag_edge_capacity(B1, N, p->topk, p->connect_tools_all, p->max_tools);
     const size_t rows = (size_t)B1 * N, ecoo = (size_t)e_cap + 1 + AG_SELF_ROWS;
-    AgSharedArgs &s = L.sh;
-    s.s_state = c.take<float>(rows * H * 3);
+    l.state = s.s_state = c.take<float>(rows * H * 3);
     s.s_delta = c.take<float>(rows * 3);
     s.s_attrs = c.take<float>(rows * 2);
     s.s_pinst = c.take<float>((size_t)B1 * n_p * (I > 0 ? I : 1));
@@ -1276,19 +1324,7 @@ static void carve_shared(Carver &c, const ag_model *m, const ag_rollout_params *
     s.blk_deg = c.take<int32_t>(rows / 256 + 2);
     s.n_rows = c.take<int>(4);
     s.n_edges = s.n_rows + 1;
-    L.pred_pos = c.take<float>(rows * 3 + 4);
-    L.pred_motion = c.take<float>(rows * 3 + 4);
-    AgEdgeArgs &e = L.e;
-    e.row_ptr = c.take<int32_t>(rows + 1);
-    e.edge_recv = c.take<int32_t>(ecoo);
-    e.edge_send = c.take<int32_t>(ecoo);
-    e.self_info = c.take<int32_t>(rows);
-    e.self_pos = c.take<int32_t>(rows);
-    e.B = B1; e.N = N; e.connect = p->connect_tools_all ? 1 : 0;
-    edge_caps(N, p->topk, e.connect, p->max_tools, &e.cap0, &e.cap);
-    carve_edges(c, e);
-    carve_forward(c, L.f, B1, N, e_cap, eterm16, true);
-    L.f.e_cap = (int)e_cap;
+    carve_step(c, l, p, B1, N, true, eterm16, true);
 }
 
 static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *state0, const float *delta, const float *attrs,
@@ -1296,14 +1332,14 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
                           const float *thr_sq, const int32_t *repeat, float *out_seq, float *state_final, void *workspace, size_t workspace_bytes,
                           hipStream_t s)
 {
-    const AgPath path = resolve_path(m, p->B + 1, p->N, p->n_instance, p->n_steps, true);
+    Lane l;
+    l.path = resolve_path(m, p->B + 1, p->N, p->n_instance, p->n_steps, true);
     Carver c(workspace, workspace_bytes);
-    SharedLayout L;
-    carve_shared(c, m, p, L, path.q16);
+    AgSharedArgs sh{};
+    carve_shared(c, m, p, sh, l, l.path.q16);
     if (!c.ok()) return fail(AG_ERR_WS, "ag_rollout (shared state): workspace %zu < %zu bytes", workspace_bytes, c.off);
-    AgSharedArgs &sh = L.sh;
-    AgFwdArgs &f = L.f;
-    AgEdgeArgs &e = L.e;
+    AgFwdArgs &f = l.f;
+    AgEdgeArgs &e = l.e;
     const int B1 = p->B + 1, N = p->N, n_p = p->n_p, H = m->cfg.n_his, Pd = m->cfg.phys_dim;
     const size_t plane = (size_t)N * 3;
     sh.B1 = B1; sh.N = N; sh.n_p = n_p; sh.n_inst = p->n_instance; sh.phys_dim = Pd; sh.H = H;
@@ -1311,21 +1347,14 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
     sh.mask = mask; sh.tool = tool_mask; sh.obj_mask = obj_mask; sh.repeat = repeat;
     sh.max_tools = p->max_tools;
     ag_launch_shared_stage(sh, s);      // internal sample 0 = the base (caller sample 0 without its tools), 1 .. B = the caller's samples; first dirty flags
-    e.mask = sh.s_mask; e.tool = sh.s_tool; e.thr_sq = sh.s_thr; e.topk = p->topk; e.variant = AG_VARIANT_BATCH; e.max_tools = p->max_tools;
-    e.pos = sh.s_state + (size_t)(H - 1) * plane;
-    e.pos_stride = (size_t)H * plane;
+    bind_edges(l, p, AG_VARIANT_BATCH, H, sh.s_mask, sh.s_tool, sh.s_thr);
     e.active = sh.active;
-    f.state = sh.s_state; f.attrs = sh.s_attrs; f.action = sh.s_delta; f.p_instance = sh.s_pinst; f.phys = Pd > 0 ? sh.s_phys : nullptr;
-    f.row_ptr = e.row_ptr; f.edge_recv = e.edge_recv; f.edge_send = e.edge_send;
-    f.pred_pos = L.pred_pos; f.pred_motion = L.pred_motion;
-    f.B = B1; f.N = N; f.n_p = n_p; f.n_inst = p->n_instance; f.phys_dim = Pd; f.pstep = m->cfg.pstep; f.clamp = m->cfg.motion_clamp;
-    setup_args(m, f, path, m->max_blocks);
+    bind_forward(m, f, B1, N, n_p, p->n_instance, sh.s_state, sh.s_attrs, sh.s_delta, sh.s_pinst, Pd > 0 ? sh.s_phys : nullptr, e.row_ptr, e.edge_recv,
+                 e.edge_send, l.pred_pos, l.pred_motion);
+    setup_args(m, f, l.path, m->max_blocks);
     const int self_rows = m->self_edges ? AG_SELF_ROWS : 0;
     if (self_rows) { e.self_attrs = f.attrs; e.self_class_row0 = f.self_class_row0; }
-    if (path.edge == AG_EDGE_H3_WS) {   // rider: the per-node input rows of the edge features (all B1 N nodes: the compact edges name their endpoints as nodes)
-        e.tab_state = f.state; e.tab_attrs = f.attrs; e.tab_pinst = f.p_instance; e.tab_out = f.edge_node_tab;
-        e.tab_n_inst = f.n_inst; e.tab_n_p = f.n_p; e.tab_status = f.status;
-    }
+    wire_tab_rider(l);                  // (the input rows of all B1 N nodes: the compact edges name their endpoints as nodes)
     run_node_encode(m, f, s);           // classification + compact encoder, once per call
     sh.row_ptr = e.row_ptr; sh.edge_send = e.edge_send; sh.self_info = self_rows ? e.self_info : nullptr; sh.node_row = f.node_row;
     sh.self_rows = self_rows; sh.self_class_row0 = f.self_class_row0;
@@ -1334,16 +1363,16 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
     fP.row_ptr = sh.row_ptr_c; fP.edge_send = sh.send_cm; fP.send_c = sh.send_r0; fP.node_row = sh.node_row_c;
     fP.self_info = self_rows ? sh.self_info_c : nullptr; fP.self_rows = self_rows;
     fP.n_rows_dev = sh.n_rows; fP.e_count_dev = sh.n_edges; fP.row_orig = sh.orig;
-    AgStepArgs st{};
-    st.state = sh.s_state; st.delta = sh.s_delta; st.pred_pos = L.pred_pos; st.obj_mask = obj_mask ? sh.s_obj_mask : nullptr;
+    AgStepArgs &st = l.st;
+    st.state = sh.s_state; st.delta = sh.s_delta; st.pred_pos = l.pred_pos; st.obj_mask = obj_mask ? sh.s_obj_mask : nullptr;
     st.repeat = sh.s_repeat; st.out_seq = out_seq; st.B = B1; st.N = N; st.n_p = n_p; st.H = H;
     st.height_mode = p->height_mode; st.raise = p->gripper_raise; st.cmap = sh.cmap; st.dirty = sh.dirty; st.sample_dirty = sh.sample_dirty;
     for (int ai = 1; ai <= p->n_steps; ++ai) {
         int riders;
         { Timed tm(m, AG_K_EDGES, s); ag_launch_shared_active(sh, s); riders = ag_launch_build_edges(e, s); ag_launch_shared_compact(sh, s); }
         fE.tab_done = (riders & AG_RIDER_TAB) != 0;
-        run_edge_encode(m, fE, path, s);
-        run_propagate(m, fP, path, s);
+        run_edge_encode(m, fE, l.path, s);
+        run_propagate(m, fP, l.path, s);
         st.step = ai;
         { Timed tm(m, AG_K_ROLLOUT_STEP, s); ag_launch_rollout_step(st, s); }
     }
@@ -1361,28 +1390,109 @@ size_t ag_rollout_workspace_bytes_for(const ag_model *m, const ag_rollout_params
     if (!p) return 0;
     // ag_rollout carves one layout per batch part and the number of parts is a model option ("rollout_streams", 1..4) the
     // caller may change between this query and the call: size for the largest of the four possible carvings, exactly.
-    const bool q16 = resolve_path(m, p->B, p->N, p->n_instance).q16;
     size_t need = 0;
+    Lane lane[AG_MAX_PARTS];
     for (int want = 1; want <= AG_MAX_PARTS; ++want) {
-        const int parts = rollout_parts(p->B, want);
         Carver c(nullptr, 0);
-        for (int k = 0; k < parts; ++k) {
-            AgFwdArgs f{};
-            AgEdgeArgs e{};
-            float *a, *b, *d;
-            int b0, nb;
-            part_range(p->B, parts, k, &b0, &nb);
-            carve_rollout(c, p, nb, f, e, &a, &b, &d, AG_NHIS, q16);
-        }
+        carve_parts(c, m, p, rollout_parts(p->B, want), lane);
         need = c.off > need ? c.off : need;
     }
     if (shared_applicable(m, p)) {      // (an option the caller may switch off again before the call: the larger of the two layouts)
         Carver c(nullptr, 0);
-        SharedLayout L;
-        carve_shared(c, m, p, L, q16);
+        AgSharedArgs sh{};
+        carve_shared(c, m, p, sh, lane[0], resolve_path(m, p->B, p->N, p->n_instance).q16);
         need = c.off > need ? c.off : need;
     }
     return align_up(need, 256);
+}
+
+struct Join {   // RAII: whichever way ag_rollout returns, the streams it forked off the caller's stream join it again (success: join(), for its code)
+    hipStream_t caller;
+    int n = 0;
+    hipEvent_t event[AG_MAX_PARTS];
+    hipStream_t forked[AG_MAX_PARTS];
+    hipError_t fork(hipStream_t stream, hipEvent_t ev_fork, hipEvent_t ev_join)     // `stream` waits on the fork event; once it does, it is joined
+    {
+        hipError_t rc = hipStreamWaitEvent(stream, ev_fork, 0);
+        if (rc == hipSuccess) { event[n] = ev_join; forked[n++] = stream; }
+        return rc;
+    }
+    hipError_t join()
+    {
+        hipError_t rc = hipSuccess;
+        for (int k = 0; k < n; ++k) {
+            hipError_t e = hipEventRecord(event[k], forked[k]);
+            if (e == hipSuccess) e = hipStreamWaitEvent(caller, event[k], 0);
+            if (rc == hipSuccess) rc = e;
+        }
+        n = 0;
+        return rc;
+    }
+    ~Join() { (void)join(); }
+};
+
+// One stream per part, the steps issued round-robin over the parts so every stream always has work queued
+static int issue_round_robin(ag_model *m, hipStream_t s0, Lane *lane, int parts, int n_steps)
+{
+    for (int ai = 1; ai <= n_steps; ++ai)
+        for (int k = 0; k < parts; ++k) {
+            Lane &l = lane[k];
+            AgFwdArgs &f = l.f;
+            // (step-invariant when de-duplicated, see run_node_encode; in front of the edge build, whose sender-map rider needs its node_row)
+            if (ai == 1 || !f.dedup) run_node_encode(m, f, l.s);
+            int riders;
+            { Timed tm(m, AG_K_EDGES, l.s); riders = ag_launch_build_edges(l.e, l.s); }
+            f.tab_done = (riders & AG_RIDER_TAB) != 0;
+            f.remap_done = (riders & AG_RIDER_MAP) != 0;
+            run_node_encode_fallback(m, f, l.s);
+            run_edge_encode(m, f, l.path, l.s);
+            if (ai == 1 && k == 0 && parts > 1) {
+                // phase offset: the other parts start once part 0 has finished its first MFMA-bound encode stage, so
+                // from then on one stream's HBM-bound segment reduce co-runs with another stream's MFMA-bound stage
+                AG_HIP(hipEventRecord(m->ev_fork, s0));
+                for (int kk = 1; kk < parts; ++kk) AG_HIP(hipStreamWaitEvent(m->aux_stream[kk], m->ev_fork, 0));
+            }
+            run_propagate(m, f, l.path, l.s);
+            l.st.step = ai;
+            { Timed tm(m, AG_K_ROLLOUT_STEP, l.s); ag_launch_rollout_step(l.st, l.s); }
+        }
+    return AG_OK;
+}
+
+// Two in-order queues with disjoint CU masks.  HBM queue (sR): edge build -> [ready] ... [encoded] -> three propagation rounds -> state step;
+// MFMA queue (sE): [ready] -> per-node input rows + edge encoder + sender remap -> [encoded].  Part k's step ai + 1 cannot start before its
+// step ai has finished (the edges are rebuilt from the predicted positions), so with two parts the steady state is
+//     sE:  E(A, i+1)  E(B, i+1)  E(A, i+2) ...          sR:  R(B, i)  R(A, i+1)  R(B, i+1) ...
+// each partition always busy with its own kind of work, the other part's.  Every table is per part, and E(k, i+1) is ordered behind
+// R(k, i) through `ready`, so nothing is overwritten while it is read.
+// Enqueue order matters (both queues are in order): a part's NEXT edge build follows its own state step directly, and the wait for the
+// encoder stands in front of the rounds that need it — not in front of the other part's edge build.
+static int issue_partitioned(ag_model *m, Lane *lane, int parts, int n_steps)
+{
+    hipStream_t sE = m->mfma_stream, sR = m->hbm_stream;
+    auto graph_of_step = [&](int k, int ai) -> int {       // sR: edge build, node encoder -> ready;  sE: ready -> edge encoder -> encoded
+        AgFwdArgs &f = lane[k].f;
+        { Timed tm(m, AG_K_EDGES, sR); ag_launch_build_edges(lane[k].e, sR); }
+        if (ai == 1 || !f.dedup) run_node_encode(m, f, sR);
+        run_node_encode_fallback(m, f, sR);
+        AG_HIP(hipEventRecord(m->ev_ready[k], sR));
+        AG_HIP(hipStreamWaitEvent(sE, m->ev_ready[k], 0));
+        run_edge_encode(m, f, lane[k].path, sE);
+        AG_HIP(hipEventRecord(m->ev_enc[k], sE));
+        return AG_OK;
+    };
+    for (int k = 0; k < parts && n_steps > 0; ++k)
+        if (int rc = graph_of_step(k, 1)) return rc;
+    for (int ai = 1; ai <= n_steps; ++ai)
+        for (int k = 0; k < parts; ++k) {
+            AG_HIP(hipStreamWaitEvent(sR, m->ev_enc[k], 0));
+            run_propagate(m, lane[k].f, lane[k].path, sR);
+            lane[k].st.step = ai;
+            { Timed tm(m, AG_K_ROLLOUT_STEP, sR); ag_launch_rollout_step(lane[k].st, sR); }
+            if (ai < n_steps)
+                if (int rc = graph_of_step(k, ai + 1)) return rc;
+        }
+    return AG_OK;
 }
 
 int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, const float *delta, const float *attrs,
@@ -1409,165 +1519,65 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
             AG_HIP(hipEventCreateWithFlags(&m->ev_join[k], hipEventDisableTiming));
         }
     if (parts > 1 && !m->ev_fork) AG_HIP(hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming));
+    Lane lane[AG_MAX_PARTS];
     Carver c(workspace, workspace_bytes);
-    struct Part { AgFwdArgs f{}; AgEdgeArgs e{}; AgPath path; float *state, *pp, *pm; int b0, B; } part[AG_MAX_PARTS];
-    for (int k = 0; k < parts; ++k) {
-        part_range(p->B, parts, k, &part[k].b0, &part[k].B);
-        part[k].path = resolve_path(m, part[k].B, N, p->n_instance, p->n_steps);
-        carve_rollout(c, p, part[k].B, part[k].f, part[k].e, &part[k].state, &part[k].pp, &part[k].pm, H, part[k].path.q16);
-    }
+    carve_parts(c, m, p, parts, lane);
     if (!c.ok()) return fail(AG_ERR_WS, "ag_rollout: workspace %zu < %zu bytes", workspace_bytes, c.off);
-    if (parts > 1) {
-        AG_HIP(hipEventRecord(m->ev_fork, s0));
-        for (int k = 1; k < parts; ++k) AG_HIP(hipStreamWaitEvent(m->aux_stream[k], m->ev_fork, 0));
-    }
+    // (needs >= 2 batch parts and the weight-stationary edge encoder for the whole batch, whose grid is one workgroup per CU)
+    const bool partitioned = m->cu_split > 0 && parts >= 2 && resolve_path(m, p->B, N, p->n_instance).edge == AG_EDGE_H3_WS;
+    if (partitioned)
+        if (int rc = ensure_partition(m)) return rc;
     const size_t plane = (size_t)N * 3;
     const int part_blocks = m->max_blocks / parts > 0 ? m->max_blocks / parts : 1;   // each part's persistent kernels take an equal share
-    // CU-partitioned pipeline (cu_split > 0; needs >= 2 batch parts and the weight-stationary edge encoder for the whole batch, whose grid is one
-    // workgroup per CU)
-    const bool partitioned = m->cu_split > 0 && parts >= 2 && resolve_path(m, p->B, N, p->n_instance).edge == AG_EDGE_H3_WS;
-    hipStream_t sE = nullptr, sR = nullptr;
-    if (partitioned) {
-        const int prc = ensure_partition(m);
-        if (prc != AG_OK) return prc;
-        sE = m->mfma_stream; sR = m->hbm_stream;
-        AG_HIP(hipStreamWaitEvent(sE, m->ev_fork, 0));
-        AG_HIP(hipStreamWaitEvent(sR, m->ev_fork, 0));
-    }
-    int rc = AG_OK;
-    // issue the steps round-robin over the parts so every stream always has work queued
-    struct Run { AgStepArgs st{}; hipStream_t s; } run[AG_MAX_PARTS];
-    for (int k = 0; k < parts && rc == AG_OK; ++k) {
-        Part &q = part[k];
-        hipStream_t s = partitioned ? sR : (k == 0 ? s0 : m->aux_stream[k]);
-        run[k].s = s;
-        const size_t b0 = (size_t)q.b0;
-        const size_t state_bytes = (size_t)q.B * H * plane * sizeof(float);
-        if (hipMemcpyAsync(q.state, state0 + b0 * H * plane, state_bytes, hipMemcpyDeviceToDevice, s) != hipSuccess) { rc = AG_ERR_HIP; break; }
-        AgEdgeArgs &e = q.e;
-        AgFwdArgs &f = q.f;
-        e.mask = mask + b0 * N; e.tool = tool_mask + b0 * N; e.thr_sq = thr_sq + b0; e.topk = p->topk;
-        e.variant = AG_VARIANT_BATCH; e.max_tools = p->max_tools;
-        e.pos = q.state + (size_t)(H - 1) * plane;     // edges on the current frame = state[:, -1] (forward_dynamics.py:125 / :171)
-        e.pos_stride = (size_t)H * plane;
-        f.state = q.state; f.attrs = attrs + b0 * N * 2; f.action = delta + b0 * plane;
-        f.p_instance = p_instance + b0 * n_p * p->n_instance; f.phys = phys ? phys + b0 * Pd : nullptr;
-        f.row_ptr = e.row_ptr; f.edge_recv = e.edge_recv; f.edge_send = e.edge_send;
-        f.pred_pos = q.pp; f.pred_motion = q.pm;
-        f.B = q.B; f.N = N; f.n_p = n_p; f.n_inst = p->n_instance; f.phys_dim = Pd;
-        f.pstep = m->cfg.pstep; f.clamp = m->cfg.motion_clamp;
+    for (int k = 0; k < parts; ++k) {      // the parts' arguments (nothing is enqueued here)
+        Lane &l = lane[k];
+        AgEdgeArgs &e = l.e;
+        AgFwdArgs &f = l.f;
+        const size_t b0 = (size_t)l.b0;
+        l.s = partitioned ? m->hbm_stream : (k == 0 ? s0 : m->aux_stream[k]);
+        bind_edges(l, p, AG_VARIANT_BATCH, H, mask + b0 * N, tool_mask + b0 * N, thr_sq + b0);
+        bind_forward(m, f, l.B, N, n_p, p->n_instance, l.state, attrs + b0 * N * 2, delta + b0 * plane, p_instance + b0 * n_p * p->n_instance,
+                     phys ? phys + b0 * Pd : nullptr, e.row_ptr, e.edge_recv, e.edge_send, l.pred_pos, l.pred_motion);
         if (m->self_edges) {      // self-edge elision: the builder leaves class-0 / class-1 self-loops out of the lists, the encoder adds one row per class
             e.self_attrs = f.attrs; e.self_class_row0 = f.self_class_row0;
             f.self_info = e.self_info; f.self_rows = AG_SELF_ROWS;
         }
-        AgStepArgs &st = run[k].st;
-        st.state = q.state; st.delta = delta + b0 * plane; st.pred_pos = q.pp;
+        if (partitioned) {
+            setup_args(m, f, l.path, AG_MLP_WG_PER_CU * (m->n_cus - m->cu_split));   // persistent node kernels: the HBM partition's CUs
+            f.ws_blocks = m->cu_split;                                                // edge encoder: one workgroup per CU of the MFMA partition
+        } else {
+            setup_args(m, f, l.path, part_blocks);
+            // riders of the edge builder's launches (one 15 us launch per model step less each): the edge encoder's per-node input rows and, for a
+            // de-duplicated node encoder, the sender column mapped to compact rows
+            wire_tab_rider(l);
+            if (f.dedup) { e.map_node_row = f.node_row; e.map_ovf = f.ovf; e.map_send_c = f.send_c; }
+        }
+        AgStepArgs &st = l.st;
+        st.state = l.state; st.delta = delta + b0 * plane; st.pred_pos = l.pred_pos;
         st.obj_mask = obj_mask ? obj_mask + b0 * n_p : nullptr; st.repeat = repeat + b0;
-        st.out_seq = out_seq + b0 * n_p * 3; st.B = q.B; st.N = N; st.n_p = n_p; st.H = H;
+        st.out_seq = out_seq + b0 * n_p * 3; st.B = l.B; st.N = N; st.n_p = n_p; st.H = H;
         st.height_mode = p->height_mode; st.raise = p->gripper_raise;
     }
-    if (partitioned) {
-        // Two in-order queues with disjoint CU masks.  HBM queue (sR): edge build -> [ready] ... [encoded] -> three propagation rounds -> state step;
-        // MFMA queue (sE): [ready] -> per-node input rows + edge encoder + sender remap -> [encoded].  Part k's step ai + 1 cannot start before its
-        // step ai has finished (the edges are rebuilt from the predicted positions), so with two parts the steady state is
-        //     sE:  E(A, i+1)  E(B, i+1)  E(A, i+2) ...          sR:  R(B, i)  R(A, i+1)  R(B, i+1) ...
-        // each partition always busy with its own kind of work, the other part's.  Every table is per part, and E(k, i+1) is ordered behind
-        // R(k, i) through `ready`, so nothing is overwritten while it is read.
-        // Enqueue order matters (both queues are in order): a part's NEXT edge build follows its own state step directly, and the wait for the
-        // encoder stands in front of the rounds that need it — not in front of the other part's edge build.
-        auto encode = [&](int k) {       // sR: [edges built] -> ready;  sE: ready -> encoder -> encoded
-            if (hipEventRecord(m->ev_ready[k], sR) != hipSuccess || hipStreamWaitEvent(sE, m->ev_ready[k], 0) != hipSuccess) return AG_ERR_HIP;
-            run_edge_encode(m, part[k].f, part[k].path, sE);
-            return hipEventRecord(m->ev_enc[k], sE) == hipSuccess ? AG_OK : AG_ERR_HIP;
-        };
-        for (int k = 0; k < parts && rc == AG_OK && p->n_steps > 0; ++k) {
-            AgFwdArgs &f = part[k].f;
-            { Timed tm(m, AG_K_EDGES, sR); ag_launch_build_edges(part[k].e, sR); }
-            setup_args(m, f, part[k].path, AG_MLP_WG_PER_CU * (m->n_cus - m->cu_split));  // persistent node kernels: the HBM partition's CUs
-            f.ws_blocks = m->cu_split;                                                     // edge encoder: one workgroup per CU of the MFMA partition
-            run_node_encode(m, f, sR);
-            run_node_encode_fallback(m, f, sR);
-            rc = encode(k);
-        }
-        for (int ai = 1; ai <= p->n_steps && rc == AG_OK; ++ai)
-            for (int k = 0; k < parts && rc == AG_OK; ++k) {
-                AgFwdArgs &f = part[k].f;
-                if (hipStreamWaitEvent(sR, m->ev_enc[k], 0) != hipSuccess) { rc = AG_ERR_HIP; break; }
-                run_propagate(m, f, part[k].path, sR);
-                run[k].st.step = ai;
-                { Timed tm(m, AG_K_ROLLOUT_STEP, sR); ag_launch_rollout_step(run[k].st, sR); }
-                if (ai < p->n_steps) {
-                    { Timed tm(m, AG_K_EDGES, sR); ag_launch_build_edges(part[k].e, sR); }
-                    if (!f.dedup) run_node_encode(m, f, sR);
-                    run_node_encode_fallback(m, f, sR);
-                    rc = encode(k);
-                }
-            }
-    } else
-    for (int ai = 1; ai <= p->n_steps && rc == AG_OK; ++ai)
-        for (int k = 0; k < parts && rc == AG_OK; ++k) {
-            hipStream_t s = run[k].s;
-            AgFwdArgs &f = part[k].f;
-            AgEdgeArgs &e = part[k].e;
-            const AgPath &path = part[k].path;
-            if (ai == 1) {
-                setup_args(m, f, path, part_blocks);
-                // Riders of the edge builder's launches (AgEdgeArgs): the per-node input rows of the weight-stationary edge encoder and, for a
-                // de-duplicated node encoder, the sender column mapped to compact rows — one 15 us launch per model step less.  The map needs
-                // node_row, so the node encoder (which does not read the edges) goes in front of the first step's edge build.
-                if (path.edge == AG_EDGE_H3_WS) {
-                    e.tab_state = f.state; e.tab_attrs = f.attrs; e.tab_pinst = f.p_instance; e.tab_out = f.edge_node_tab;
-                    e.tab_n_inst = f.n_inst; e.tab_n_p = f.n_p; e.tab_status = f.status;
-                }
-                if (f.dedup) { e.map_node_row = f.node_row; e.map_ovf = f.ovf; e.map_send_c = f.send_c; }
-            }
-            if (ai == 1 || !f.dedup) run_node_encode(m, f, s);       // step-invariant when de-duplicated (see run_node_encode)
-            int riders;
-            { Timed tm(m, AG_K_EDGES, s); riders = ag_launch_build_edges(e, s); }
-            f.tab_done = (riders & AG_RIDER_TAB) != 0;
-            f.remap_done = (riders & AG_RIDER_MAP) != 0;
-            run_node_encode_fallback(m, f, s);
-            run_edge_encode(m, f, path, s);
-            if (ai == 1 && k == 0 && parts > 1) {
-                // phase offset: the other parts start once part 0 has finished its first MFMA-bound encode stage, so
-                // from then on one stream's HBM-bound segment reduce co-runs with another stream's MFMA-bound stage
-                if (hipEventRecord(m->ev_fork, s0) != hipSuccess) { rc = AG_ERR_HIP; break; }
-                for (int kk = 1; kk < parts; ++kk)
-                    if (hipStreamWaitEvent(m->aux_stream[kk], m->ev_fork, 0) != hipSuccess) rc = AG_ERR_HIP;
-                if (rc != AG_OK) break;
-            }
-            run_propagate(m, f, path, s);
-            run[k].st.step = ai;
-            { Timed tm(m, AG_K_ROLLOUT_STEP, s); ag_launch_rollout_step(run[k].st, s); }
-        }
-    for (int k = 0; k < parts && rc == AG_OK && state_final; ++k) {
-        const size_t b0 = (size_t)part[k].b0;
-        if (hipMemcpyAsync(state_final + b0 * H * plane, part[k].state, (size_t)part[k].B * H * plane * sizeof(float),
-                           hipMemcpyDeviceToDevice, run[k].s) != hipSuccess)
-            rc = AG_ERR_HIP;
-    }
-    // every exit path joins the auxiliary streams back into the caller's stream
-    if (partitioned) {
-        if (hipEventRecord(m->ev_join_mfma, sE) != hipSuccess || hipStreamWaitEvent(s0, m->ev_join_mfma, 0) != hipSuccess ||
-            hipEventRecord(m->ev_join[1], sR) != hipSuccess || hipStreamWaitEvent(s0, m->ev_join[1], 0) != hipSuccess)
-            rc = AG_ERR_HIP;
-    } else
+    Join join{s0};
+    if (parts > 1) AG_HIP(hipEventRecord(m->ev_fork, s0));
     for (int k = 1; k < parts; ++k)
-        if (hipEventRecord(m->ev_join[k], m->aux_stream[k]) != hipSuccess || hipStreamWaitEvent(s0, m->ev_join[k], 0) != hipSuccess)
-            rc = AG_ERR_HIP;
-    if (rc != AG_OK) return fail(rc, "ag_rollout: a HIP runtime call failed: %s", hipGetErrorString(hipGetLastError()));
+        if (partitioned) AG_HIP(hipStreamWaitEvent(m->aux_stream[k], m->ev_fork, 0));    // (the part streams wait on the fork and get no work)
+        else AG_HIP(join.fork(m->aux_stream[k], m->ev_fork, m->ev_join[k]));
+    if (partitioned) {      // (joined in this order: the MFMA queue, then the HBM queue)
+        AG_HIP(join.fork(m->mfma_stream, m->ev_fork, m->ev_join_mfma));
+        AG_HIP(join.fork(m->hbm_stream, m->ev_fork, m->ev_join[1]));
+    }
+    for (const Lane *l = lane; l < lane + parts; ++l)
+        AG_HIP(hipMemcpyAsync(l->state, state0 + (size_t)l->b0 * H * plane, (size_t)l->B * H * plane * sizeof(float), hipMemcpyDeviceToDevice, l->s));
+    if (int rc = partitioned ? issue_partitioned(m, lane, parts, p->n_steps) : issue_round_robin(m, s0, lane, parts, p->n_steps)) return rc;
+    for (const Lane *l = lane; l < lane + parts && state_final; ++l)
+        AG_HIP(hipMemcpyAsync(state_final + (size_t)l->b0 * H * plane, l->state, (size_t)l->B * H * plane * sizeof(float), hipMemcpyDeviceToDevice, l->s));
+    AG_HIP(join.join());
     AG_HIP(hipGetLastError());
     return AG_OK;
 }
 
 // ---- scripted rollout (ag_scripted.hip): per step exactly the launches of ag_build_edges + ag_forward, then the scripted state update -------------
-struct ScriptedLayout {
-    AgFwdArgs f{};
-    AgEdgeArgs e{};
-    float *state, *action, *pred_pos, *pred_motion;
-    int64_t e_cap;
-};
-
 static bool scripted_sizes_ok(const ag_scripted_params *p)
 {
     return p->B >= 1 && p->N >= 1 && p->n_p >= 1 && p->n_p <= p->N && p->n_instance >= 0 && p->topk >= 1 && p->topk <= 64 && p->max_tools >= 0 &&
@@ -1575,31 +1585,22 @@ static bool scripted_sizes_ok(const ag_scripted_params *p)
            ag_edge_capacity(p->B, p->N, p->topk, p->connect_tools_all, p->max_tools) <= 0x7fffffff;
 }
 
-static void carve_scripted(Carver &c, const ag_scripted_params *p, ScriptedLayout &L, bool eterm16)
+// its layout (the forward is ag_forward's: no self-edge elision); returns the buffer of the next step's action, which the state update writes
+static float *carve_scripted(Carver &c, const ag_scripted_params *p, Lane &l, bool eterm16)
 {
     const size_t rows = (size_t)p->B * p->N;
-    L.e_cap = ag_edge_capacity(p->B, p->N, p->topk, p->connect_tools_all, p->max_tools);
-    L.state = c.take<float>(rows * AG_NHIS * 3);
-    L.action = c.take<float>(rows * 3);
-    L.pred_pos = c.take<float>((size_t)p->B * p->n_p * 3 + 4);
-    L.pred_motion = c.take<float>((size_t)p->B * p->n_p * 3 + 4);
-    AgEdgeArgs &e = L.e;
-    e.row_ptr = c.take<int32_t>(rows + 1);
-    e.edge_recv = c.take<int32_t>((size_t)L.e_cap + 1);
-    e.edge_send = c.take<int32_t>((size_t)L.e_cap + 1);
-    e.B = p->B; e.N = p->N; e.connect = p->connect_tools_all ? 1 : 0;
-    edge_caps(p->N, p->topk, e.connect, p->max_tools, &e.cap0, &e.cap);
-    carve_edges(c, e);
-    carve_forward(c, L.f, p->B, p->N, L.e_cap, eterm16);
-    L.f.e_cap = (int)L.e_cap;
+    l.state = c.take<float>(rows * AG_NHIS * 3);
+    float *action = c.take<float>(rows * 3);
+    carve_step(c, l, p, p->B, p->n_p, false, eterm16);
+    return action;
 }
 
 size_t ag_rollout_scripted_workspace_bytes_for(const ag_model *m, const ag_scripted_params *p)
 {
     if (!p || !scripted_sizes_ok(p)) return 0;
     Carver c(nullptr, 0);
-    ScriptedLayout L;
-    carve_scripted(c, p, L, resolve_path(m, p->B, p->N, p->n_instance).q16);
+    Lane l;
+    carve_scripted(c, p, l, resolve_path(m, p->B, p->N, p->n_instance).q16);
     return align_up(c.off, 256);
 }
 
@@ -1622,43 +1623,38 @@ int ag_rollout_scripted(ag_model *m, const ag_scripted_params *p, const float *s
         return fail(AG_ERR_ARG, "ag_rollout_scripted: null tool script (%d tool slots, %d steps)", p->N - p->n_p, p->n_steps);
     if (m->cfg.phys_dim > 0 && !phys) return fail(AG_ERR_ARG, "ag_rollout_scripted: phys is null");
     // the path of an ag_forward call of this batch (one model step per forward: the node inputs change every step, nothing is hoisted)
-    const AgPath path = resolve_path(m, p->B, p->N, p->n_instance);
+    Lane l;
+    l.path = resolve_path(m, p->B, p->N, p->n_instance);
     Carver c(workspace, workspace_bytes);
-    ScriptedLayout L;
-    carve_scripted(c, p, L, path.q16);
+    float *action = carve_scripted(c, p, l, l.path.q16);
     // (against the query's rounded-up figure: a buffer one byte short of what the query asked for is refused, whatever the carving's last offset)
     if (!c.ok() || workspace_bytes < align_up(c.off, 256))
         return fail(AG_ERR_WS, "ag_rollout_scripted: workspace %zu < %zu bytes", workspace_bytes, align_up(c.off, 256));
     hipStream_t s = static_cast<hipStream_t>(stream);
     const int N = p->N, n_p = p->n_p, T = p->n_steps;
     const size_t plane = (size_t)N * 3, state_bytes = (size_t)p->B * AG_NHIS * plane * sizeof(float);
-    AG_HIP(hipMemcpyAsync(L.state, state0, state_bytes, hipMemcpyDeviceToDevice, s));
-    AgEdgeArgs &e = L.e;
-    e.mask = mask; e.tool = tool_mask; e.thr_sq = thr_sq; e.topk = p->topk; e.variant = p->variant; e.max_tools = p->max_tools;
-    e.pos = L.state + (size_t)(AG_NHIS - 1) * plane;      // edges on the current frame = state[:, -1]
-    e.pos_stride = (size_t)AG_NHIS * plane;
-    AgFwdArgs &f = L.f;
-    f.state = L.state; f.attrs = attrs; f.p_instance = p_instance; f.phys = phys;
-    f.row_ptr = e.row_ptr; f.edge_recv = e.edge_recv; f.edge_send = e.edge_send;
-    f.pred_pos = L.pred_pos; f.pred_motion = L.pred_motion;
-    f.B = p->B; f.N = N; f.n_p = n_p; f.n_inst = p->n_instance; f.phys_dim = m->cfg.phys_dim;
-    f.pstep = m->cfg.pstep; f.clamp = m->cfg.motion_clamp;
-    setup_args(m, f, path, m->max_blocks);
+    AG_HIP(hipMemcpyAsync(l.state, state0, state_bytes, hipMemcpyDeviceToDevice, s));
+    AgEdgeArgs &e = l.e;
+    AgFwdArgs &f = l.f;
+    bind_edges(l, p, p->variant, AG_NHIS, mask, tool_mask, thr_sq);
+    bind_forward(m, f, p->B, N, n_p, p->n_instance, l.state, attrs, action0, p_instance, phys, e.row_ptr, e.edge_recv, e.edge_send, l.pred_pos,
+                 l.pred_motion);
+    setup_args(m, f, l.path, m->max_blocks);
     AgScriptArgs st{};
-    st.state = L.state; st.action = L.action; st.pred_pos = L.pred_pos; st.tool_pos = tool_pos; st.tool_delta = tool_delta;
+    st.state = l.state; st.action = action; st.pred_pos = l.pred_pos; st.tool_pos = tool_pos; st.tool_delta = tool_delta;
     st.gt = gt; st.obj_mask = obj_mask; st.pred_seq = pred_seq; st.err = err;
     st.B = p->B; st.N = N; st.n_p = n_p; st.T = T;
     for (int t = 0; t < T; ++t) {
         { Timed tm(m, AG_K_EDGES, s); ag_launch_build_edges(e, s); }
-        f.action = t == 0 ? action0 : L.action;
+        f.action = t == 0 ? action0 : action;
         run_node_encode(m, f, s);
         run_node_encode_fallback(m, f, s);
-        run_edge_encode(m, f, path, s);
-        run_propagate(m, f, path, s);
+        run_edge_encode(m, f, l.path, s);
+        run_propagate(m, f, l.path, s);
         st.t = t;
         { Timed tm(m, AG_K_ROLLOUT_STEP, s); ag_launch_scripted_step(st, s); }
     }
-    if (state_final) AG_HIP(hipMemcpyAsync(state_final, L.state, state_bytes, hipMemcpyDeviceToDevice, s));
+    if (state_final) AG_HIP(hipMemcpyAsync(state_final, l.state, state_bytes, hipMemcpyDeviceToDevice, s));
     AG_HIP(hipGetLastError());
     return AG_OK;
 }

@@ -135,6 +135,42 @@ def test_version_and_capacity_queries():
     assert L.ag_edges_workspace_bytes(256, 1001, 10, 0, 1) >= 256 * 1001 * 11 * 4
 
 
+# (B, N, n_p, n_instance, topk, connect_tools_all, max_tools) -> ag_edge_capacity, ag_edges_workspace_bytes, ag_forward_workspace_bytes,
+# ag_rollout_workspace_bytes, ag_rollout_scripted_workspace_bytes_for(NULL); n_steps 4, height mode 0, builder variant "batch".
+# Recorded from the library before the rollout drivers shared one carving of a step's graph buffers.
+WORKSPACE_BYTES = {
+    (1, 2, 1, 1, 10, 0, 1): (4, 34560, 4038400, 4075520, 4074752),
+    (7, 9, 8, 1, 5, 1, 1): (378, 234496, 4203264, 4446720, 4446464),
+    (8, 301, 300, 1, 10, 0, 1): (24080, 408064, 30014208, 30818560, 30827520),
+    (16, 301, 300, 1, 20, 0, 1): (96320, 1007360, 87566592, 93209088, 89769216),
+    (31, 65, 64, 2, 5, 1, 1): (12090, 1146880, 20847872, 29435904, 22268928),
+    (33, 257, 256, 0, 64, 0, 0): (542784, 3424512, 392628992, 412413440, 401142784),
+    (256, 1001, 1000, 1, 10, 0, 1): (2562560, 23778304, 2862914816, 2931705856, 2929739264),
+    (2, 4101, 4096, 1, 5, 1, 5): (82020, 723200, 94052096, 96122112, 96154112),
+}
+
+
+def workspace_queries(model, B, N, n_p, n_inst, topk, connect, max_tools):
+    """The five sizes of one WORKSPACE_BYTES row, for `model` (a handle, or None: any model)."""
+    L = _lib.lib()
+    e_cap = L.ag_edge_capacity(B, N, topk, connect, max_tools)
+    rollout = _lib.RolloutParams(B, N, n_p, n_inst, topk, connect, max_tools, 4, _lib.AG_HEIGHT_MIN, 0.0)
+    scripted = _lib.ScriptedParams(B, N, n_p, n_inst, topk, connect, max_tools, _lib.AG_VARIANT_BATCH, 4)
+    return (e_cap, L.ag_edges_workspace_bytes(B, N, topk, connect, max_tools), L.ag_forward_workspace_bytes_for(model, B, N, e_cap),
+            L.ag_rollout_workspace_bytes_for(model, ctypes.byref(rollout)), L.ag_rollout_scripted_workspace_bytes_for(model, ctypes.byref(scripted)))
+
+
+def test_model_less_workspace_sizes_are_the_recorded_ones():
+    """Every carving of a workspace keeps its offsets: 1 to 4 possible batch parts and the cap B / parts >= 8, edge lists with and without the
+    tail of elided self-loops, connect_tools_all, n_instance 0 and 2, and a top-k clipped to N."""
+    L = _lib.lib()
+    for row, want in WORKSPACE_BYTES.items():
+        assert workspace_queries(None, *row) == want, row
+        prm = _lib.RolloutParams(*row, 4, _lib.AG_HEIGHT_MIN, 0.0)
+        assert L.ag_rollout_workspace_bytes(ctypes.byref(prm)) == want[3], row
+        assert L.ag_forward_workspace_bytes(row[0], row[1], want[0]) == want[2], row
+
+
 def test_errors_are_codes_not_crashes():
     L = _lib.lib()
     h = ctypes.c_void_p()

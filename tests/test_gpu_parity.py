@@ -1168,6 +1168,92 @@ def test_rollout_stream_count_default_follows_the_workload_and_never_changes_a_b
         m.set_option("rollout_streams", 5)
 
 
+def test_every_driver_launches_what_its_loop_says(weights):
+    """Launches per kernel class (ag_profile_read) of one call of every driver, through the C ABI: T model steps of S propagation rounds, P batch
+    parts.  The node encoder runs once per part when its inputs are de-duplicated (they do not change during a rollout), every step otherwise and
+    in the scripted rollout (its action changes); the fused reduce has no launch of its own; the shared-state rollout is one part.  The
+    one-stream, the two-stream and the CU-partitioned rollout walk the same graphs: the same, non-zero, number of edges.  (The library's counter
+    adds, per edge encoder launch of a rollout with self-edge elision, the class rows that stand for the elided self-loops — AG_SELF_ROWS,
+    csrc/ag_common.h —, and two parts launch twice as often: 3616 = 3424 + 3 x 64 on one stream, 3808 = 3424 + 6 x 64 on two.  The
+    graphs' own edges are compared.)"""
+    import ctypes
+    import re
+    header = open(os.path.join(_lib.CSRC, "ag_common.h")).read()
+    classes, repl = (int(re.search(r"#define %s (\d+)" % name, header).group(1)) for name in ("AG_SELF_CLASSES", "AG_SELF_REPL"))
+    self_rows = classes * repl                 # AG_SELF_ROWS
+    B, n_p, T, topk = 16, 32, 3, 10            # the smallest batch two parts exist for (B / parts >= 8)
+    N, S = n_p + 1, configs.model_config()["pstep"]
+    g = synth.make_graph_inputs("rope", n_p, B, seed=3)
+    dev = torch.device(DEV)
+    m = make_model(weights, "rope", prec="fast")
+    L, h = _lib.lib(), m.handle(dev)
+    state, attrs, action, pinst, phys = (t(g[k]) for k in ("state", "attrs", "action", "p_instance", "phys"))
+    mask, tool = (t(g[k]).view(torch.uint8) for k in ("mask", "tool_mask"))
+    thr = aggraph.threshold_sq(0.5, B, dev, _lib.AG_VARIANT_BATCH)
+    repeat = torch.full((B,), T, dtype=torch.int32, device=DEV)
+
+    def counted(call):
+        _lib.check(L.ag_profile_enable(h, 1), "ag_profile_enable")
+        call()
+        torch.cuda.synchronize()
+        ms, cnt, edges = (ctypes.c_double * 6)(), (ctypes.c_int64 * 6)(), ctypes.c_int64()
+        _lib.check(L.ag_profile_read(h, ms, cnt, ctypes.byref(edges)), "ag_profile_read")
+        _lib.check(L.ag_profile_enable(h, 0), "ag_profile_enable")
+        return tuple(cnt), edges.value
+
+    def rollout_call():
+        prm = _lib.RolloutParams(B, N, n_p, 1, topk, 0, 1, T, _lib.AG_HEIGHT_MIN, 0.0)
+        ws = _lib.workspace(dev, L.ag_rollout_workspace_bytes_for(h, ctypes.byref(prm)))
+        out = torch.zeros((B, n_p, 3), device=DEV)
+        _lib.call("ag_rollout", dev, h, ctypes.byref(prm), state, action, attrs, pinst, phys, mask, tool, None, thr, repeat, out, None, ws, ws.numel())
+
+    def scripted_call():
+        prm = _lib.ScriptedParams(B, N, n_p, 1, topk, 0, 1, _lib.AG_VARIANT_BATCH, T)
+        ws = _lib.workspace(dev, L.ag_rollout_scripted_workspace_bytes_for(h, ctypes.byref(prm)))
+        tool_pos = state[:, -1, n_p:].unsqueeze(1).repeat(1, T, 1, 1).contiguous()
+        tool_delta = action[:, n_p:].unsqueeze(1).repeat(1, T, 1, 1).contiguous()
+        pred = torch.empty((B, T, n_p, 3), device=DEV)
+        _lib.call("ag_rollout_scripted", dev, h, ctypes.byref(prm), state, action, tool_pos, tool_delta, attrs, pinst, phys, mask, tool, thr, None,
+                  None, pred, None, None, ws, ws.numel())
+
+    def forward_call():
+        e_cap = L.ag_edge_capacity(B, N, topk, 0, 1)
+        row_ptr = torch.empty(B * N + 1, dtype=torch.int32, device=DEV)
+        recv, send = (torch.empty(e_cap, dtype=torch.int32, device=DEV) for _ in range(2))
+        ws = _lib.workspace(dev, max(L.ag_edges_workspace_bytes(B, N, topk, 0, 1), L.ag_forward_workspace_bytes_for(h, B, N, e_cap)))
+        _lib.call("ag_build_edges", dev, state[:, -1].contiguous(), mask, tool, thr, topk, 0, _lib.AG_VARIANT_BATCH, B, N, 1, row_ptr, recv, send,
+                  e_cap, ws, ws.numel())
+        pos, mot = (torch.empty((B, n_p, 3), device=DEV) for _ in range(2))
+        _lib.call("ag_forward", dev, h, state, attrs, action, pinst, 1, phys, row_ptr, recv, send, e_cap, B, N, n_p, pos, mot, ws, ws.numel())
+
+    def per_part(P, encodes, aggregates=T * S):      # (build_edges, node_encode, edge_encode, aggregate, node_update, rollout_step)
+        return (P * T, P * encodes, P * T, P * aggregates, P * T * S, P * T)
+
+    assert _lib.KERNEL_CLASSES == ("build_edges", "node_encode", "edge_encode", "aggregate", "node_update", "rollout_step")
+    cases = [   # options on top of the default model, the call, its launches
+        ({"rollout_streams": 1, "node_dedup": 2}, rollout_call, per_part(1, 1)),
+        ({"rollout_streams": 1, "node_dedup": 0}, rollout_call, per_part(1, T)),
+        ({"rollout_streams": 2, "node_dedup": 2}, rollout_call, per_part(2, 1)),
+        ({"rollout_streams": 2, "node_dedup": 2, "cu_split": 32}, rollout_call, per_part(2, 1)),
+        ({"rollout_streams": 1, "shared_state": 1}, rollout_call, per_part(1, 1)),
+        ({"rollout_streams": 1, "node_dedup": 2, "fuse_aggregate": 2}, rollout_call, per_part(1, 1, aggregates=0)),
+        ({}, scripted_call, per_part(1, T)),
+        ({}, forward_call, (0, 1, 1, S, S, 0)),
+    ]
+    defaults = {name: m.get_option(name) for name in ("rollout_streams", "node_dedup", "cu_split", "shared_state", "fuse_aggregate")}
+    edges = []
+    for options, call, want in cases:
+        for name, value in {**defaults, **options}.items():
+            m.set_option(name, value)
+            assert m.get_option(name) == value, name
+        cnt, e = counted(call)
+        print(options, call.__name__, cnt, e)
+        assert cnt == want, (options, call.__name__)
+        edges.append(e - self_rows * cnt[2])      # (rollouts with self-edge elision: see above)
+    assert m.take_status() == 0
+    assert edges[0] > 0 and edges[0] == edges[2] == edges[3], edges
+
+
 def test_rollout_is_hip_graph_capturable(weights):
     """ag_rollout never synchronises the host and joins its auxiliary streams on every path, so a caller may capture it in a HIP graph
     (torch.cuda.graphs): the replayed rollout equals the enqueued one bit for bit, twice (replay is not faster, the point is
@@ -1382,6 +1468,36 @@ def test_workspace_is_bounded_and_sized_for_the_models_mode(weights):
     assert torch.isfinite(mot).all() and not bool((mot == 7.0).all())
     m.set_option("precision", 1)
     assert call() == -3 and b"workspace" in L.ag_last_error()
+
+
+# ag_rollout_workspace_bytes_for / ag_rollout_scripted_workspace_bytes_for of a model, n_steps 4: (B, N, n_p, n_instance, topk, connect_tools_all,
+# max_tools) -> the two sizes.  Recorded on an MI355X from the library before the rollout drivers shared one carving of a step's graph buffers.
+MODEL_WORKSPACE_BYTES = {
+    "default": {(8, 301, 300, 1, 10, 0, 1): (23118080, 23127040), (16, 301, 300, 1, 20, 0, 1): (62407168, 58967296)},
+    "precision 0": {(8, 301, 300, 1, 10, 0, 1): (30818560, 30827520), (16, 301, 300, 1, 20, 0, 1): (93209088, 89769216)},
+    "shared_state 1": {(8, 301, 300, 1, 10, 0, 1): (30809088, 23127040), (16, 301, 300, 1, 20, 0, 1): (74985216, 58967296)},
+}
+
+
+def test_workspace_sizes_of_a_model_are_the_recorded_ones(weights):
+    """The layouts a model's options select keep their offsets: 16-bit per-edge rows (default mode), fp32 rows (precision 0), and the
+    shared-state layout beside the per-part ones."""
+    import ctypes
+    L = _lib.lib()
+    got = {}
+    for name in MODEL_WORKSPACE_BYTES:
+        m = make_model(weights, prec="fast")
+        if name != "default":
+            option, value = name.split()
+            m.set_option(option, int(value))
+        h = m.handle(torch.device(DEV))
+        got[name] = {}
+        for row in MODEL_WORKSPACE_BYTES[name]:
+            rollout = _lib.RolloutParams(*row, 4, _lib.AG_HEIGHT_MIN, 0.0)
+            scripted = _lib.ScriptedParams(*row, _lib.AG_VARIANT_BATCH, 4)
+            got[name][row] = (L.ag_rollout_workspace_bytes_for(h, ctypes.byref(rollout)), L.ag_rollout_scripted_workspace_bytes_for(h, ctypes.byref(scripted)))
+    print(got)
+    assert got == MODEL_WORKSPACE_BYTES
 
 
 @pytest.mark.parametrize("n_obj", [300, 1000])
