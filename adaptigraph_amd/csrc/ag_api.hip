@@ -1202,7 +1202,7 @@ int ag_forward(ag_model *m, const float *state, const float *attrs, const float 
                const int32_t *edge_send, int64_t e_cap, int B, int N, int n_p, float *pred_pos, float *pred_motion,
                void *workspace, size_t workspace_bytes, ag_stream_t stream)
 {
-    if (!m || !state || !attrs || !action || !p_instance || !row_ptr || !edge_recv || !edge_send || !pred_pos ||
+    if (!m || !state || !attrs || !action || (!p_instance && n_instance > 0) || !row_ptr || !edge_recv || !edge_send || !pred_pos ||
         !pred_motion || !workspace)
         return fail(AG_ERR_ARG, "ag_forward: null argument");
     if (m->cfg.phys_dim > 0 && !phys) return fail(AG_ERR_ARG, "ag_forward: phys is null");
@@ -1500,7 +1500,7 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
                const uint8_t *obj_mask, const float *thr_sq, const int32_t *repeat, float *out_seq,
                float *state_final, void *workspace, size_t workspace_bytes, ag_stream_t stream)
 {
-    if (!m || !p || !state0 || !delta || !attrs || !p_instance || !mask || !tool_mask || !thr_sq || !repeat ||
+    if (!m || !p || !state0 || !delta || !attrs || (!p_instance && p->n_instance > 0) || !mask || !tool_mask || !thr_sq || !repeat ||
         !out_seq || !workspace)
         return fail(AG_ERR_ARG, "ag_rollout: null argument");
     if (p->height_mode == AG_HEIGHT_MASKED_MEAN && !obj_mask) return fail(AG_ERR_ARG, "ag_rollout: obj_mask is null");
@@ -1609,7 +1609,7 @@ int ag_rollout_scripted(ag_model *m, const ag_scripted_params *p, const float *s
                         const uint8_t *tool_mask, const float *thr_sq, const float *gt, const uint8_t *obj_mask, float *pred_seq, float *err,
                         float *state_final, void *workspace, size_t workspace_bytes, ag_stream_t stream)
 {
-    if (!m || !p || !state0 || !action0 || !attrs || !p_instance || !mask || !tool_mask || !thr_sq || !workspace)
+    if (!m || !p || !state0 || !action0 || !attrs || (!p_instance && p->n_instance > 0) || !mask || !tool_mask || !thr_sq || !workspace)
         return fail(AG_ERR_ARG, "ag_rollout_scripted: null argument");
     if (p->n_steps < 1) return fail(AG_ERR_ARG, "ag_rollout_scripted: n_steps=%d (>= 1)", p->n_steps);
     if (p->n_p > p->N || p->topk < 1 || p->topk > 64)

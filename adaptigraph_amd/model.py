@@ -94,9 +94,15 @@ class DynamicsPredictor(nn.Module):
     def _signature(self):
         return tuple((p.data_ptr(), p._version) for p in self.parameters())
 
-    def _sync_weights(self):
+    def sync_weights(self, force=False):
+        """Bring the engine's packed weights up to date with the parameters; every call that needs the model's handle does this first.
+        A change is detected by each parameter's (data_ptr, version counter): `load_state_dict`, `.to(device)`, an optimiser step or any
+        in-place edit under `torch.no_grad()` is picked up on the next call, at no cost on the hot path (no checksum, no launch).
+        Edits that BYPASS the version counter are not seen — `p.data.mul_(2)`, `p.data.copy_(w)` (`.data` is a view with a counter of its
+        own) or a write through a raw pointer leave the engine running the old weights: call `model.sync_weights(force=True)` after such
+        an edit.  `force=True` repacks unconditionally (ag_model_update_weights: a host repack, a device synchronisation and one upload)."""
         sig = self._signature()
-        if self._handle is not None and sig == self._sig:
+        if self._handle is not None and sig == self._sig and not force:
             return
         L = _lib.lib()
         sd = self.state_dict()
@@ -115,7 +121,7 @@ class DynamicsPredictor(nn.Module):
 
     def handle(self, device):
         with torch.cuda.device(device):
-            self._sync_weights()
+            self.sync_weights()
         return self._handle
 
     def take_status(self, device=None):

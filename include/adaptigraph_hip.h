@@ -175,6 +175,7 @@ size_t ag_forward_workspace_bytes_for(const ag_model *m, int B, int N, int64_t e
 
 /* DynamicsPredictor.forward (model.py:129-313) on a CSR adjacency instead of one-hot Rr/Rs.
  *   state (B,n_his,N,3), attrs (B,N,2), action (B,N,3), p_instance (B,n_p,n_instance), phys (B,phys_dim)
+ *   (p_instance may be NULL when n_instance is 0, phys when phys_dim is 0: an empty tensor has no address; the same holds for the rollouts)
  *   row_ptr/edge_recv/edge_send as produced by ag_build_edges (edges sorted by receiver).
  * Out: pred_pos, pred_motion (B,n_p,3). */
 int ag_forward(ag_model *m, const float *state, const float *attrs, const float *action, const float *p_instance,
