@@ -20,6 +20,9 @@ KERNEL_CLASSES = ("build_edges", "node_encode", "edge_encode", "aggregate", "nod
 
 AG_VARIANT_SINGLE, AG_VARIANT_BATCH = 0, 1
 AG_HEIGHT_MIN, AG_HEIGHT_MASKED_MEAN = 0, 1
+AG_PENALTIES = {None: 0, "rope": 1, "cloth": 2, "granular": 3}      # AG_PENALTY_*
+AG_ERROR_GIVEN, AG_ERROR_BOX = 0, 1
+AG_PLAN_TERMS = 9
 
 c_void_p, c_char_p, c_int, c_int32, c_int64, c_size_t, c_float, c_double, P = (
     ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double,
@@ -49,6 +52,11 @@ class RolloutParams(ctypes.Structure):
 
 class ScriptedParams(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int32) for n in ("B", "N", "n_p", "n_instance", "topk", "connect_tools_all", "max_tools", "variant", "n_steps")]
+
+
+class PlanCostParams(ctypes.Structure):
+    _fields_ = [("B", ctypes.c_int32), ("L", ctypes.c_int32), ("n", ctypes.c_int32), ("penalty", ctypes.c_int32), ("criterion", ctypes.c_int32),
+                ("sim_real_ratio", ctypes.c_float), ("bbox", ctypes.c_float * 4), ("box", ctypes.c_float * 4)]
 
 
 # The C ABI, one row per export in the order and the groups of include/adaptigraph_hip.h: name -> (restype, [argtypes]).
@@ -94,6 +102,9 @@ SIGNATURES = {
     "ag_chamfer_tiled_workspace_bytes": (c_size_t, [c_int] * 3),
     "ag_chamfer_tiled": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "ag_chamfer_tiled_backward": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3),
+    # the planner's trajectory cost
+    "ag_plan_cost_workspace_bytes": (c_size_t, [P(PlanCostParams)]),
+    "ag_plan_cost": (c_int, [P(PlanCostParams)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
     # farthest-point sampling
     "ag_fps_workspace_bytes": (c_size_t, [c_int] * 2),
     "ag_fps": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]),

@@ -823,6 +823,49 @@ int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float
     return AG_OK;
 }
 
+// ---- the planner's trajectory cost (ag_plan_cost.hip) ----
+static const char *plan_cost_refusal(const ag_plan_cost_params *p)
+{
+    if (!p) return "null parameters";
+    if (p->B < 1 || p->L < 1 || p->n < 1) return "B, L and n must be at least 1";
+    if ((long long)p->B * p->L > (1LL << 30)) return "B * L exceeds 2^30 clouds";
+    if (p->penalty < AG_PENALTY_NONE || p->penalty > AG_PENALTY_GRANULAR) return "unknown penalty";
+    if (p->criterion != AG_ERROR_GIVEN && p->criterion != AG_ERROR_BOX) return "unknown criterion";
+    return nullptr;
+}
+
+// the per-(b, l) term table of a call that passes no `terms`
+size_t ag_plan_cost_workspace_bytes(const ag_plan_cost_params *p)
+{
+    if (plan_cost_refusal(p)) return 0;
+    return align_up((size_t)p->B * p->L * AG_PLAN_TERMS * sizeof(float), 256);
+}
+
+int ag_plan_cost(const ag_plan_cost_params *p, const float *state_seqs, const float *action, const float *state_init, const float *error_in,
+                 float *reward, float *terms, void *ws, size_t ws_bytes, ag_stream_t stream)
+{
+    const char *who = "ag_plan_cost";
+    if (const char *why = plan_cost_refusal(p))
+        return fail(AG_ERR_ARG, "%s: %s (B=%d L=%d n=%d penalty=%d criterion=%d)", who, why, p ? p->B : 0, p ? p->L : 0, p ? p->n : 0,
+                    p ? p->penalty : 0, p ? p->criterion : 0);
+    if (!state_seqs || !action || !state_init || !reward) return fail(AG_ERR_ARG, "%s: null argument", who);
+    if (p->criterion == AG_ERROR_GIVEN && !error_in) return fail(AG_ERR_ARG, "%s: AG_ERROR_GIVEN needs error_in", who);
+    const size_t need = ag_plan_cost_workspace_bytes(p);
+    if (!ws || ws_bytes < need) return fail(AG_ERR_WS, "%s: workspace %zu < %zu bytes", who, ws ? ws_bytes : (size_t)0, need);
+    AgPlanCostArgs a{};
+    a.state_seqs = state_seqs; a.action = action; a.state_init = state_init; a.error_in = error_in;
+    a.reward = reward;
+    a.terms = terms ? terms : static_cast<float *>(ws);
+    a.B = p->B; a.L = p->L; a.n = p->n; a.penalty = p->penalty; a.box_criterion = p->criterion == AG_ERROR_BOX;
+    // the reference's thresholds are Python doubles (0.05 * sim_real_ratio ...) that a tensor op rounds to float once
+    const double r = (double)p->sim_real_ratio;
+    a.rad = (float)(0.05 * r); a.touch = (float)(0.02 * r); a.grasp = (float)(0.005 * r); a.far_cap = (float)(0.4 * r);
+    for (int i = 0; i < 4; ++i) { a.bbox[i] = p->bbox[i]; a.box[i] = p->box[i]; }
+    ag_launch_plan_cost(a, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 // kept distances of the streaming form: one float per point of every cloud (asked of every call, so that the caller's buffer never depends on which
 // form the library picks for a size)
 size_t ag_fps_workspace_bytes(int B, int N)

@@ -594,3 +594,13 @@ int ag_launch_chamfer_tiled(const float *x, const float *y, const unsigned char 
 int ag_launch_chamfer_tiled_backward(const float *x, const unsigned char *xmask, const float *y, const unsigned char *ymask, const int *idx_x,
                                      const int *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy,
                                      hipStream_t s);
+// the planner's trajectory cost (ag_plan_cost.hip): one wave per (b, l) cloud, then one workgroup for the normalisers and the rewards.
+// The thresholds are the reference's Python doubles rounded to float once, as a tensor op rounds its scalar operand.
+struct AgPlanCostArgs {
+    const float *state_seqs, *action, *state_init, *error_in;      // (B, L, n, 3), (B, L, 4), (n, 3), (B L) or NULL
+    float *reward, *terms;                                         // (B), (B, L, AG_PLAN_TERMS): the caller's table or the workspace
+    int B, L, n, penalty, box_criterion;
+    float rad, touch, grasp, far_cap;                              // 0.05 r, 0.02 r, 0.005 r, 0.4 r
+    float bbox[4], box[4];
+};
+void ag_launch_plan_cost(const AgPlanCostArgs &a, hipStream_t s);

@@ -1,7 +1,8 @@
 """Trajectory cost terms of the planner — drop-in for src/planning/losses.py.
 
-`chamfer` runs the HIP kernel (`ag_chamfer`: no (B,M,N,3) temporaries); the penalties are a few element-wise ops
-over (bsz, n_look_forward, n_obj) and stay as device tensor ops.
+`chamfer` runs the HIP kernel (`ag_chamfer`: no (B,M,N,3) temporaries).  The penalties and `box_loss` here are tensor ops over
+(bsz, n_look_forward, n_obj) temporaries: the reference's arithmetic, the autograd path of `GradientPlanner`, and the form that runs on
+CPU tensors.  A planner that only scores samples gets the same terms from one device call, `mpc.running_cost_fused` (`ag_plan_cost`).
 """
 import torch
 

@@ -6,11 +6,12 @@ with the rollout sharded over the ranks of the process group when one is initial
 and `Planner`'s iteration read nothing back (the reference's `error.max().item()` normaliser is a 0-d tensor here and the best
 sample is picked with a device-side `index_select`, not with a 0-d tensor index, which PyTorch resolves through `.item()`).
 """
+import ctypes
 import functools
 
 import torch
 
-from . import losses
+from . import _lib, losses
 from .dist import dynamics_sharded, replicate
 from .forward_dynamics import dynamics
 from .plan_utils import clip_actions, optimize_action_mppi, sample_action_seq
@@ -28,6 +29,65 @@ def running_cost(state, action, state_cur, error_func, penalty_func, bbox, **kwa
     box = torch.exp(-margins.clamp_min(0) * 100.0).max(dim=-1).values             # 1 when a particle sits on the workspace edge
     reward = -error_weight * error[:, -1] - 5.0 * collision.mean(dim=1) - 5.0 * box.mean(dim=1)
     return {"reward_seqs": reward}
+
+
+_PENALTY_FUNCS = {"rope": losses.rope_penalty, "cloth": losses.cloth_penalty, "granular": losses.granular_penalty}
+
+
+def _no_penalty(state, action, state_cur):
+    return torch.zeros(state.shape[:2], dtype=state.dtype, device=state.device)
+
+
+def running_cost_fused(state, action, state_cur, bbox, penalty, sim_real_ratio=10.0, error_func=None, box_target=None, return_terms=False,
+                       **kwargs):
+    """`running_cost` as ONE device call (`ag_plan_cost`: two launches that read every predicted cloud once, no (bsz, L, n) temporaries, no host
+    read): state (bsz, L, n, 3), action (bsz, L, 4), state_cur (n, 3), bbox [[xmin,xmax],[zmin,zmax]] -> {"reward_seqs": (bsz,)} and, with
+    return_terms, "terms" (bsz, L, 9): error, collision, box, nearest, farthest pusher distance, xlo, xhi, zlo, zhi per cloud.
+
+    penalty: "rope", "cloth", "granular" (the `losses.*_penalty` of that name at `sim_real_ratio`) or None (no collision term).
+    Exactly one of error_func (a callable on (bsz * L, n, 3) as for `running_cost`, e.g. partial(losses.chamfer, y=target): its result goes
+    in as the error term) and box_target ((2, 2): the `losses.box_loss` criterion, computed in the same pass).
+
+    No backward: with grad mode on and `state` or `action` requiring grad, and for CPU tensors, this IS `running_cost` with the tensor-op
+    penalty and criterion (the same values as before)."""
+    if (error_func is None) == (box_target is None):
+        raise ValueError("running_cost_fused: give exactly one of error_func and box_target")
+    if penalty not in _lib.AG_PENALTIES:
+        raise ValueError(f"running_cost_fused: penalty {penalty!r} is not one of 'rope', 'cloth', 'granular', None")
+    if not state.is_cuda or (torch.is_grad_enabled() and (state.requires_grad or action.requires_grad)):
+        if error_func is None:
+            error_func = functools.partial(losses.box_loss, target=torch.as_tensor(box_target, dtype=state.dtype, device=state.device))
+        penalty_func = functools.partial(_PENALTY_FUNCS[penalty], sim_real_ratio=sim_real_ratio) if penalty else _no_penalty
+        if return_terms:
+            raise NotImplementedError("running_cost_fused: the per-cloud terms come from the device call (no autograd, no CPU tensors)")
+        return running_cost(state, action, state_cur, error_func, penalty_func, bbox)
+    dev = state.device
+    bsz, L, n = state.shape[0], state.shape[1], state.shape[2]
+    assert state.dim() == 4 and state.shape[3] == 3 and action.shape[:2] == (bsz, L) and action.shape[2] >= (3 if penalty == "granular" else 2)
+    state = state.detach().contiguous().float()
+    act = action.detach().to(dev).float()
+    if act.shape[2] != 4:                        # the kernel reads (x_start, z_start, theta, length) rows
+        act = torch.nn.functional.pad(act[:, :, :4], (0, max(0, 4 - act.shape[2])))
+    act = act.contiguous()
+    init = state_cur.detach().to(dev).contiguous().float()
+    assert init.shape == (n, 3)
+    error = None
+    if error_func is not None:
+        error = error_func(state.reshape(bsz * L, n, 3)).detach().reshape(bsz * L).contiguous().float()
+    prm = _lib.PlanCostParams(bsz, L, n, _lib.AG_PENALTIES[penalty], _lib.AG_ERROR_GIVEN if box_target is None else _lib.AG_ERROR_BOX,
+                              float(sim_real_ratio))
+    prm.bbox[:] = [float(v) for v in torch.as_tensor(bbox, dtype=torch.float32).reshape(4).tolist()]
+    if box_target is not None:
+        prm.box[:] = [float(v) for v in torch.as_tensor(box_target, dtype=torch.float32).reshape(4).tolist()]
+    reward = torch.empty(bsz, dtype=torch.float32, device=dev)
+    terms = torch.empty((bsz, L, _lib.AG_PLAN_TERMS), dtype=torch.float32, device=dev) if return_terms else None
+    nbytes = _lib.lib().ag_plan_cost_workspace_bytes(ctypes.byref(prm))
+    ws = _lib.workspace(dev, nbytes)
+    _lib.call("ag_plan_cost", dev, ctypes.byref(prm), state, act, init, error, reward, terms, ws, nbytes)
+    res = {"reward_seqs": reward}
+    if return_terms:
+        res["terms"] = terms
+    return res
 
 
 class Planner:
@@ -188,7 +248,7 @@ class MPPIPlanner:
 
     def __init__(self, model, device, ppm_optimizer, error_func, penalty_func, bbox, action_lower_lim, action_upper_lim,
                  n_sample, n_look_ahead=1, n_update_iter=1, reward_weight=500.0, noise_level=1.0, rollout_best=True, n_sample_chunk=None,
-                 shared_state=True):
+                 shared_state=True, penalty=None, box_target=None, sim_real_ratio=None):
         task = ppm_optimizer.task_config
         # Every rollout of this planner is ONE cloud under many sampled pushes (planner.py:246): let the engine roll the tool-less base trajectory out
         # once and compute per sample only what can differ from it (ag_set_option "shared_state"; same bits, 8x fewer ms at 1 024 x 15 on rope-1k).
@@ -210,6 +270,12 @@ class MPPIPlanner:
         # fine for one rollout scored right away, not for chunked rollouts that are concatenated afterwards
         self.model_rollout = lambda state, acts, copy=True: dynamics_sharded(dynamics, state, acts, model, device, ppm_optimizer, copy=copy)
         self.evaluate_traj = functools.partial(running_cost, error_func=error_func, penalty_func=penalty_func, bbox=bbox)
+        # Opt-in: score with ONE device call (running_cost_fused) instead of the tensor ops.  penalty ("rope" / "cloth" / "granular") replaces
+        # penalty_func, box_target (a (2, 2) box) replaces error_func; sim_real_ratio defaults to the task's.  With neither given nothing changes.
+        if penalty is not None or box_target is not None:
+            ratio = task.get("sim_real_ratio", 10.0) if sim_real_ratio is None else sim_real_ratio
+            self.evaluate_traj = functools.partial(running_cost_fused, bbox=bbox, penalty=penalty, sim_real_ratio=ratio,
+                                                   error_func=None if box_target is not None else error_func, box_target=box_target)
 
     def sample(self, act_seq, iter_index, device=None):
         """Sampled action sequences, REPLICATED across the process group: every rank scores the gathered rollouts of all

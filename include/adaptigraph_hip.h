@@ -299,6 +299,46 @@ int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float
                               const int32_t *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy,
                               ag_stream_t stream);
 
+/* ---- the planner's trajectory cost ("MPPI glue on device"): everything of running_cost, src/planning/plan.py:27-59, but the
+ * error term's own kernel — the penalties rope_penalty / cloth_penalty / granular_penalty and box_loss of src/planning/losses.py:26-92, the
+ * workspace-bounds term of plan.py:41-51 and the reward of plan.py:37 and 53 — in two launches that read every predicted cloud once.
+ *   state_seqs (B, L, n, 3), action (B, L, 4) = (x_start, z_start, theta, length), state_init (n, 3), error_in (B*L) or NULL, all fp32.
+ * Per cloud (b, l), in the x-z plane, every product and sum rounded separately, d(p, q) the distance of two points:
+ *   extents    xlo, xhi, zlo, zhi = min / max over the n particles
+ *   error      AG_ERROR_GIVEN: error_in[b L + l].  AG_ERROR_BOX: box_loss(state_seqs[b, l], box) = the mean over the particles (ascending
+ *              per lane, then a butterfly: one fixed order) of sqrt(dx dx + dz dz), dx = max(box xmin - x, 0) + max(x - box xmax, 0)
+ *   nearest    the particles of the cloud BEFORE push l (state_init for l = 0, state_seqs[b, l - 1] after; cloth: always state_init) against
+ *              rope / cloth: the start point of action (b, l); granular: the nine points start + off (r sin theta, -r cos theta),
+ *              off = -1, -0.75 ... 1, r = 0.05 sim_real_ratio.  The square root of the smallest squared distance (= the smallest distance)
+ *   farthest   cloth: the largest such distance; else 0
+ *   collision  rope, granular: exp(-100 max(nearest - 0.02 ratio, 0));  none: 0
+ *              cloth: 1 - exp(-100 max(nearest - 0.005 ratio, 0)) - 0.2 f / max over all (b, l) of f,  f = min(farthest, 0.4 ratio)
+ *   box        the largest of exp(-100 max(margin, 0)) over the margins xlo - bbox xmin, bbox xmax - xhi, zlo - bbox zmin, bbox zmax - zhi
+ * and per sample, evaluated left to right, the means as ascending-l sums divided by L:
+ *   reward[b] = -(2 / (max over all (b, l) of error + 1e-6)) error[b, L - 1] - 5 mean_l collision - 5 mean_l box.
+ * A NaN goes where the reference's tensor ops carry it (min, max, mean and clamp propagate NaN there): a NaN x or z coordinate makes the
+ * cloud's extents, box term, box_loss and the next push's nearest distance NaN, and a NaN error makes every reward NaN.  y is not read.
+ * terms: NULL, or (B, L, AG_PLAN_TERMS): error, collision, box, nearest, farthest, xlo, xhi, zlo, zhi of every (b, l).
+ * ws: ag_plan_cost_workspace_bytes(p) bytes (AG_ERR_WS otherwise), 4-byte aligned; holds the per-(b, l) terms of a call without `terms`; every
+ * word is written before it is read.  No host synchronisation, no memset, no atomics: the call can be captured in a HIP graph and returns the
+ * same bits every time. ---- */
+enum { AG_PENALTY_NONE = 0, AG_PENALTY_ROPE = 1, AG_PENALTY_CLOTH = 2, AG_PENALTY_GRANULAR = 3 };
+enum { AG_ERROR_GIVEN = 0, AG_ERROR_BOX = 1 };
+#define AG_PLAN_TERMS 9
+typedef struct ag_plan_cost_params {
+    int B, L, n;
+    int penalty;      /* AG_PENALTY_NONE / _ROPE / _CLOTH / _GRANULAR */
+    int criterion;    /* AG_ERROR_GIVEN: error_in (B*L) is the error term (e.g. from ag_chamfer); AG_ERROR_BOX: box_loss against box[] */
+    float sim_real_ratio;
+    float bbox[4];    /* xmin, xmax, zmin, zmax of the workspace */
+    float box[4];     /* target box of AG_ERROR_BOX */
+} ag_plan_cost_params;
+
+/* Scratch of ag_plan_cost: AG_PLAN_TERMS floats per (b, l), whatever n; 0 for parameters the call refuses. */
+size_t ag_plan_cost_workspace_bytes(const ag_plan_cost_params *p);
+int ag_plan_cost(const ag_plan_cost_params *p, const float *state_seqs, const float *action, const float *state_init,
+                 const float *error_in, float *reward, float *terms, void *ws, size_t ws_bytes, ag_stream_t stream);
+
 /* ---- farthest-point key-point sampling (SURVEY.md §8f row n3 data side): the two passes of fps() of src/dynamics/dataset/graph.py:8-36 — the
  * first is dgl.geometry.farthest_point_sampler, the second fps_rad_idx of src/dynamics/utils.py:10-24 — and with them the perception step of
  * the closed loop, src/planning/perception.py:266-279.  B clouds in one launch, one workgroup per cloud.
