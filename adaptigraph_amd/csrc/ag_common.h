@@ -47,7 +47,7 @@ struct AgWeights {           // device pointers into the packed weight streams (
     // the same streams as split-bf16 fragment images (precision AG_PREC_B3)
     const float4 *node_encode_b3, *edge_encode_b3, *node_mid_b3, *node_last_b3;
     // the edge stream of the fp16 edge stack (precision mode 2, PrecH3): chunk 0 = the first layer as a split-fp16 fragment image, chunks 1..15 =
-    // the wide units as [hi fp16 fragments | block-scaled fp8 A operands] (ag_api.hip pack_layer_h3), and their block scales (128 dwords per unit)
+    // the wide units as [hi fp16 fragments | block-scaled fp8 A operands] (ag_pack.hip pack_layer_h3), and their block scales (128 dwords per unit)
     const float4 *edge_encode_h2;
     const uint32_t *edge_scale_h3;
 };
@@ -101,7 +101,7 @@ struct AgFwdArgs {
     int *priv_count, *ovf;           // device words, zeroed with enc_count; ovf == NULL: no de-duplication in this call
     int shared_rows;                 // = B * AG_DEDUP_REPS: first private row
     const float *hr_full, *hs_full;  // round 0 only: the full-size tables the per-node encoder writes (read instead of hr / hs when *ovf)
-    // per-launch views set by the sequencer (ag_api.hip: run_propagate)
+    // per-launch views set by the sequencer (ag_engine.hip: run_propagate)
     const int32_t *hr_row;           // segment reduce: row of Hr to read for node g (NULL: g) — node_row in round 0
     const float *pn_rows;            // node_update: Pn from compact rows pn_rows[node_row[g]] (NULL: packed table pn)
     const float *h_rows;             // node_update, round 0: residual h from compact rows (NULL: packed table h)
@@ -355,7 +355,7 @@ __device__ __forceinline__ void ag_reduce_node_q16(const AgFwdArgs &a, int g, in
     if (a.status && !isfinite(((acc0.x + acc0.y) + (acc0.z + acc0.w)) + ((acc1.x + acc1.y) + (acc1.z + acc1.w)))) atomicOr(a.status, 1);
 }
 
-// The kernels one forward runs, decided once per call from the model's options and the call's shape (ag_api.hip: resolve_path); the
+// The kernels one forward runs, decided once per call from the model's options and the call's shape (ag_engine.hip: resolve_path); the
 // launchers and the sequencer dispatch on it and re-derive nothing.  Edge encoder: fp32 MFMA (precision 0), split-bf16, or the fp16 edge stack with
 // residual bytes (precision 2, "edge_products" 2) on the streaming or the weight-stationary kernel.
 enum AgEdgeEncoder { AG_EDGE_F32, AG_EDGE_B3, AG_EDGE_H3, AG_EDGE_H3_WS };

@@ -735,7 +735,7 @@ __global__ __launch_bounds__(256) void finalize_connect_sweep_kernel(AgEdgeArgs 
 }
 
 // ---- exclusive scan of the per-row degrees -> row_ptr, then COO fill -----------------------------
-constexpr int kScanRows = 256;    // rows per block (one per thread; ag_api.hip sizes blk_sum with the same number)
+constexpr int kScanRows = 256;    // rows per block (one per thread; ag_engine.hip sizes blk_sum with the same number)
 
 // Self-edge elision (AgEdgeArgs::self_attrs): a row's self-loop is left out of the lists when the node's attribute pair is class 0 / 1
 // (ag_self_class).  Its position in the (ascending) sender row is found here — the workgroup's 256 rows staged through LDS with coalesced

@@ -541,7 +541,7 @@ struct PrecB3 {
 // ---------------------------------------------------------------------------------------------------------------------
 // H3: the arithmetic of the EDGE stack in precision mode 2 — fp16 with byte-sized corrections on the block-scaled fp8 MFMA.
 //   weight      W = hi + lo:  hi = fp16(W);  the corrections use e4m3(lo / s_lo) and e4m3(hi / s_hi) with one power-of-two scale per
-//               (output row, 32-column input tile) (packed on the host: ag_api.hip pack_layer_h3)
+//               (output row, 32-column input tile) (packed on the host: ag_pack.hip pack_layer_h3)
 //   activation  x = x16 + r:  x16 = fp16(x) (RNE);  r8 = e5m2(x - x16) (RNE): ONE byte per value;  x8 = the top byte of x16 (= e5m2, truncated)
 //   per 32-column input tile t of an out-tile:
 //       acc += hi . x16   two v_mfma_f32_32x32x16_f16 (k16-steps 2t, 2t + 1)
@@ -562,7 +562,7 @@ struct PrecB3 {
 // FIRST layer of the edge stack: its 17 inputs + bias column use 18 of the 32 K slots of two k16-steps.  Twelve of the inputs are
 // position / velocity differences of any size (a tool joined to every cloth particle by connect_tools_all sits metres away: |x| ~ 50
 // rounds to fp16 with an error of 0.01).  Spare slots 18..29 carry the fp16 rounding residuals of inputs 5..16 against the same weight
-// columns (ag_api.hip pack_first_layer), so the first layer sees them to 2^-22 on two plain fp16 products (split-fp16 weights).
+// columns (ag_pack.hip pack_first_layer), so the first layer sees them to 2^-22 on two plain fp16 products (split-fp16 weights).
 #define AG_EDGE_LO_SLOT0 (AG_EDGE_IN + 1)       // first residual slot
 #define AG_EDGE_LO_FEAT0 (2 * AG_ATTR + 1)      // first input with a residual: the state differences (model.py:241-253)
 #define AG_EDGE_LO_COUNT (AG_EDGE_IN - AG_EDGE_LO_FEAT0)

@@ -102,10 +102,10 @@ def test_dynamic_symbol_table_is_exactly_the_header():
 
 
 def test_every_engine_option_is_one_table_row_documented_in_the_header():
-    """ag_set_option, ag_get_option and ag_model_create's environment all go through one option table (csrc/ag_api.hip: kOptions), one row per
+    """ag_set_option, ag_get_option and ag_model_create's environment all go through one option table (csrc/ag_model.hip: kOptions), one row per
     option (name, environment variable, field, validation), so the names set and get accept are the same by construction; each option and its
     environment variable is described in the header's option list (a caller of the C ABI has nothing else to go by)."""
-    src = open(os.path.join(ROOT, "adaptigraph_amd", "csrc", "ag_api.hip")).read()
+    src = open(os.path.join(ROOT, "adaptigraph_amd", "csrc", "ag_model.hip")).read()
     table = src[src.index("const Option kOptions[] = {"):src.index("};", src.index("const Option kOptions[] = {"))]
     rows = re.findall(r'\{"([a-z0-9_]+)", "(AG_[A-Z0-9_]+)", &ag_model::[a-z0-9_]+, ', table)
     names, envs = [r[0] for r in rows], [r[1] for r in rows]

@@ -1,5 +1,5 @@
 """Debug: compare the q16 per-edge table written by the weight-stationary and the streaming edge encoder on one forward golden
-(workspace layout mirrored from csrc/ag_api.hip carve_forward).   python tools/eterm_diff.py [golden]"""
+(workspace layout mirrored from csrc/ag_engine.hip carve_forward).   python tools/eterm_diff.py [golden]"""
 import os, sys
 import numpy as np, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
