@@ -59,6 +59,11 @@ class PlanCostParams(ctypes.Structure):
                 ("sim_real_ratio", ctypes.c_float), ("bbox", ctypes.c_float * 4), ("box", ctypes.c_float * 4)]
 
 
+class MppiParams(ctypes.Structure):
+    _fields_ = [("n_chunk", ctypes.c_int32), ("S", ctypes.c_int32), ("L", ctypes.c_int32), ("reward_weight", ctypes.c_float),
+                ("push_length", ctypes.c_float), ("lo", ctypes.c_float * 4), ("hi", ctypes.c_float * 4)]
+
+
 # The C ABI, one row per export in the order and the groups of include/adaptigraph_hip.h: name -> (restype, [argtypes]).
 # Device pointers, model handles and streams are c_void_p; HOST arrays and structs are typed pointers.
 # tests/test_abi.py holds every row to the header's prototype, position by position.
@@ -105,6 +110,9 @@ SIGNATURES = {
     # the planner's trajectory cost
     "ag_plan_cost_workspace_bytes": (c_size_t, [P(PlanCostParams)]),
     "ag_plan_cost": (c_int, [P(PlanCostParams)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    # a planning step's chunks in one pass
+    "ag_plan_cost_chunked": (c_int, [P(PlanCostParams), c_int] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "ag_mppi_update": (c_int, [P(MppiParams)] + [c_void_p] * 7),
     # farthest-point sampling
     "ag_fps_workspace_bytes": (c_size_t, [c_int] * 2),
     "ag_fps": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]),

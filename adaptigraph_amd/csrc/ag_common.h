@@ -603,4 +603,15 @@ struct AgPlanCostArgs {
     float rad, touch, grasp, far_cap;                              // 0.05 r, 0.02 r, 0.005 r, 0.4 r
     float bbox[4], box[4];
 };
-void ag_launch_plan_cost(const AgPlanCostArgs &a, hipStream_t s);
+// n_chunk > 1: the reward launch takes its maxima per chunk of B / n_chunk samples (one workgroup each); the terms launch is the same
+void ag_launch_plan_cost(const AgPlanCostArgs &a, int n_chunk, hipStream_t s);
+// the MPPI update of every chunk of a planning step (ag_mppi.hip): one workgroup per chunk
+struct AgMppiArgs {
+    const float *actions, *reward;                                 // (C S, L, 4), (C S)
+    float *new_seq, *best_seq, *best_reward;                       // (C, L, 4), (C, L, 4), (C); each may be NULL
+    int *best_idx;                                                 // (C) or NULL
+    int n_chunk, S, L;
+    float reward_weight, push_length;
+    float lo[4], hi[4];
+};
+void ag_launch_mppi_update(const AgMppiArgs &a, hipStream_t s);

@@ -127,13 +127,15 @@ size_t ag_plan_cost_workspace_bytes(const ag_plan_cost_params *p)
     return align_up((size_t)p->B * p->L * AG_PLAN_TERMS * sizeof(float), 256);
 }
 
-int ag_plan_cost(const ag_plan_cost_params *p, const float *state_seqs, const float *action, const float *state_init, const float *error_in,
-                 float *reward, float *terms, void *ws, size_t ws_bytes, ag_stream_t stream)
+static int plan_cost_call(const char *who, const ag_plan_cost_params *p, int n_chunk, const float *state_seqs, const float *action,
+                          const float *state_init, const float *error_in, float *reward, float *terms, void *ws, size_t ws_bytes,
+                          ag_stream_t stream)
 {
-    const char *who = "ag_plan_cost";
     if (const char *why = plan_cost_refusal(p))
         return ag_fail(AG_ERR_ARG, "%s: %s (B=%d L=%d n=%d penalty=%d criterion=%d)", who, why, p ? p->B : 0, p ? p->L : 0, p ? p->n : 0,
                     p ? p->penalty : 0, p ? p->criterion : 0);
+    if (n_chunk < 1 || p->B % n_chunk != 0)
+        return ag_fail(AG_ERR_ARG, "%s: B=%d is not n_chunk=%d chunks of S >= 1 samples each", who, p->B, n_chunk);
     if (!state_seqs || !action || !state_init || !reward) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
     if (p->criterion == AG_ERROR_GIVEN && !error_in) return ag_fail(AG_ERR_ARG, "%s: AG_ERROR_GIVEN needs error_in", who);
     const size_t need = ag_plan_cost_workspace_bytes(p);
@@ -147,7 +149,41 @@ int ag_plan_cost(const ag_plan_cost_params *p, const float *state_seqs, const fl
     const double r = (double)p->sim_real_ratio;
     a.rad = (float)(0.05 * r); a.touch = (float)(0.02 * r); a.grasp = (float)(0.005 * r); a.far_cap = (float)(0.4 * r);
     for (int i = 0; i < 4; ++i) { a.bbox[i] = p->bbox[i]; a.box[i] = p->box[i]; }
-    ag_launch_plan_cost(a, static_cast<hipStream_t>(stream));
+    ag_launch_plan_cost(a, n_chunk, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_plan_cost(const ag_plan_cost_params *p, const float *state_seqs, const float *action, const float *state_init, const float *error_in,
+                 float *reward, float *terms, void *ws, size_t ws_bytes, ag_stream_t stream)
+{
+    return plan_cost_call("ag_plan_cost", p, 1, state_seqs, action, state_init, error_in, reward, terms, ws, ws_bytes, stream);
+}
+
+int ag_plan_cost_chunked(const ag_plan_cost_params *p, int n_chunk, const float *state_seqs, const float *action, const float *state_init,
+                         const float *error_in, float *reward, float *terms, void *ws, size_t ws_bytes, ag_stream_t stream)
+{
+    return plan_cost_call("ag_plan_cost_chunked", p, n_chunk, state_seqs, action, state_init, error_in, reward, terms, ws, ws_bytes, stream);
+}
+
+// ---- the MPPI update of every chunk of a planning step (ag_mppi.hip) ----
+int ag_mppi_update(const ag_mppi_params *p, const float *actions, const float *reward, float *new_seq, int32_t *best_idx, float *best_seq,
+                   float *best_reward, ag_stream_t stream)
+{
+    const char *who = "ag_mppi_update";
+    if (!p) return ag_fail(AG_ERR_ARG, "%s: null parameters", who);
+    if (p->n_chunk < 1 || p->S < 1 || p->L < 1)
+        return ag_fail(AG_ERR_ARG, "%s: n_chunk, S and L must be at least 1 (n_chunk=%d S=%d L=%d)", who, p->n_chunk, p->S, p->L);
+    if ((long long)p->n_chunk * p->S > (1LL << 30) || (long long)p->n_chunk * p->S * p->L > (1LL << 30))
+        return ag_fail(AG_ERR_ARG, "%s: n_chunk * S * L exceeds 2^30 (n_chunk=%d S=%d L=%d)", who, p->n_chunk, p->S, p->L);
+    if (!actions || !reward) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
+    AgMppiArgs a{};
+    a.actions = actions; a.reward = reward;
+    a.new_seq = new_seq; a.best_idx = best_idx; a.best_seq = best_seq; a.best_reward = best_reward;
+    a.n_chunk = p->n_chunk; a.S = p->S; a.L = p->L;
+    a.reward_weight = p->reward_weight; a.push_length = p->push_length;
+    for (int i = 0; i < 4; ++i) { a.lo[i] = p->lo[i]; a.hi[i] = p->hi[i]; }
+    ag_launch_mppi_update(a, static_cast<hipStream_t>(stream));
     AG_HIP(hipGetLastError());
     return AG_OK;
 }

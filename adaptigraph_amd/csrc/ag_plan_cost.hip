@@ -11,6 +11,9 @@
 // plan_reward_kernel: one workgroup; max(error) and (cloth) max(dmax) over all (b, l), then the reward per sample exactly as plan.py:37 and 53 write
 // it.  Every sum and every reduction has one fixed order: the same bits on every call.
 //
+// plan_reward_chunk_kernel (ag_plan_cost_chunked): the same device function, one workgroup per chunk of S samples over that chunk's rows of the
+// table — each thread meets the rows it would meet in a call on the chunk alone, in the same order, so the chunk's rewards are that call's bits.
+//
 // NaN: torch's min / max / mean / clamp carry a NaN, fminf / fmaxf drop it.  The reductions below are written as compares that keep one
 // (nan_min / nan_max, keep_pos, cap_at), so that a diverged sample gets a NaN reward as in the reference, never a good one.
 #include "../../include/adaptigraph_hip.h"
@@ -173,15 +176,16 @@ __global__ __launch_bounds__(64 * kPlanWaves) void plan_terms_kernel(const AgPla
     }
 }
 
+// the rewards of the nb samples from b0 on, by one workgroup: both maxima are taken over these samples' rows of the table and over no others
 template <bool CLOTH>
-__global__ __launch_bounds__(kRewardThreads) void plan_reward_kernel(const AgPlanCostArgs a)
+__device__ __forceinline__ void plan_reward_rows(const AgPlanCostArgs &a, int b0, int nb)
 {
     __shared__ float red[2][kRewardThreads / 64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const long long BL = (long long)a.B * a.L;
+    const long long c0 = (long long)b0 * a.L, BL = (long long)nb * a.L;
     float emax = -INFINITY, fmax_ = -INFINITY;
     for (long long c = tid; c < BL; c += kRewardThreads) {
-        const float *t = a.terms + (size_t)c * AG_PLAN_TERMS;
+        const float *t = a.terms + (size_t)(c0 + c) * AG_PLAN_TERMS;
         emax = nan_max(emax, t[0]);
         if constexpr (CLOTH) fmax_ = nan_max(fmax_, cap_at(t[4], a.far_cap));
     }
@@ -195,7 +199,7 @@ __global__ __launch_bounds__(kRewardThreads) void plan_reward_kernel(const AgPla
     for (int w = 1; w < kRewardThreads / 64; ++w) { emax = nan_max(emax, red[0][w]); fmax_ = nan_max(fmax_, red[1][w]); }
     const float weight = 2.0f / (emax + 1e-6f);
     const float count = (float)a.L;
-    for (int b = tid; b < a.B; b += kRewardThreads) {
+    for (int b = b0 + tid; b < b0 + nb; b += kRewardThreads) {
         float *t = a.terms + (size_t)b * a.L * AG_PLAN_TERMS;
         float csum = 0.f, bsum = 0.f, err = 0.f;
         for (int l = 0; l < a.L; ++l, t += AG_PLAN_TERMS) {
@@ -215,6 +219,19 @@ __global__ __launch_bounds__(kRewardThreads) void plan_reward_kernel(const AgPla
     }
 }
 
+template <bool CLOTH>
+__global__ __launch_bounds__(kRewardThreads) void plan_reward_kernel(const AgPlanCostArgs a)
+{
+    plan_reward_rows<CLOTH>(a, 0, a.B);
+}
+
+// the planner's chunks (plan.py:241-247: one trajectory_optimization each): workgroup c scores the S samples of chunk c as a call of their own
+template <bool CLOTH>
+__global__ __launch_bounds__(kRewardThreads) void plan_reward_chunk_kernel(const AgPlanCostArgs a, int S)
+{
+    plan_reward_rows<CLOTH>(a, blockIdx.x * S, S);
+}
+
 template <int PEN>
 void launch_terms(const AgPlanCostArgs &a, dim3 grid, hipStream_t s)
 {
@@ -224,7 +241,7 @@ void launch_terms(const AgPlanCostArgs &a, dim3 grid, hipStream_t s)
 
 }  // namespace
 
-void ag_launch_plan_cost(const AgPlanCostArgs &a, hipStream_t s)
+void ag_launch_plan_cost(const AgPlanCostArgs &a, int n_chunk, hipStream_t s)
 {
     const long long BL = (long long)a.B * a.L;
     const dim3 grid((unsigned)((BL + kPlanWaves - 1) / kPlanWaves));
@@ -234,6 +251,14 @@ void ag_launch_plan_cost(const AgPlanCostArgs &a, hipStream_t s)
     case AG_PENALTY_GRANULAR: launch_terms<AG_PENALTY_GRANULAR>(a, grid, s); break;
     default: launch_terms<AG_PENALTY_NONE>(a, grid, s); break;
     }
-    if (a.penalty == AG_PENALTY_CLOTH) hipLaunchKernelGGL(plan_reward_kernel<true>, dim3(1), dim3(kRewardThreads), 0, s, a);
-    else hipLaunchKernelGGL(plan_reward_kernel<false>, dim3(1), dim3(kRewardThreads), 0, s, a);
+    const bool cloth = a.penalty == AG_PENALTY_CLOTH;
+    if (n_chunk > 1) {
+        const int S = a.B / n_chunk;
+        if (cloth) hipLaunchKernelGGL(plan_reward_chunk_kernel<true>, dim3(n_chunk), dim3(kRewardThreads), 0, s, a, S);
+        else hipLaunchKernelGGL(plan_reward_chunk_kernel<false>, dim3(n_chunk), dim3(kRewardThreads), 0, s, a, S);
+    } else if (cloth) {
+        hipLaunchKernelGGL(plan_reward_kernel<true>, dim3(1), dim3(kRewardThreads), 0, s, a);
+    } else {
+        hipLaunchKernelGGL(plan_reward_kernel<false>, dim3(1), dim3(kRewardThreads), 0, s, a);
+    }
 }

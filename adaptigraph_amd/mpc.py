@@ -14,7 +14,8 @@ import torch
 from . import _lib, losses
 from .dist import dynamics_sharded, replicate
 from .forward_dynamics import dynamics
-from .plan_utils import clip_actions, optimize_action_mppi, sample_action_seq
+from .plan_utils import (clip_actions, optimize_action_mppi, optimize_action_mppi_chunks, sample_action_seq,
+                         sample_action_seq_chunks)
 
 
 def running_cost(state, action, state_cur, error_func, penalty_func, bbox, **kwargs):
@@ -50,17 +51,28 @@ def running_cost_fused(state, action, state_cur, bbox, penalty, sim_real_ratio=1
 
     No backward: with grad mode on and `state` or `action` requiring grad, and for CPU tensors, this IS `running_cost` with the tensor-op
     penalty and criterion (the same values as before)."""
+    return _fused_cost("running_cost_fused", state, action, state_cur, None, bbox, penalty, sim_real_ratio, error_func, box_target, return_terms)
+
+
+def _fused_cost(who, state, action, state_cur, n_chunk, bbox, penalty, sim_real_ratio, error_func, box_target, return_terms):
+    """`running_cost_fused` (n_chunk None) and `running_cost_chunked`: the checks, the tensor-op route, the device call."""
     if (error_func is None) == (box_target is None):
-        raise ValueError("running_cost_fused: give exactly one of error_func and box_target")
+        raise ValueError(f"{who}: give exactly one of error_func and box_target")
     if penalty not in _lib.AG_PENALTIES:
-        raise ValueError(f"running_cost_fused: penalty {penalty!r} is not one of 'rope', 'cloth', 'granular', None")
+        raise ValueError(f"{who}: penalty {penalty!r} is not one of 'rope', 'cloth', 'granular', None")
     if not state.is_cuda or (torch.is_grad_enabled() and (state.requires_grad or action.requires_grad)):
         if error_func is None:
             error_func = functools.partial(losses.box_loss, target=torch.as_tensor(box_target, dtype=state.dtype, device=state.device))
         penalty_func = functools.partial(_PENALTY_FUNCS[penalty], sim_real_ratio=sim_real_ratio) if penalty else _no_penalty
         if return_terms:
-            raise NotImplementedError("running_cost_fused: the per-cloud terms come from the device call (no autograd, no CPU tensors)")
-        return running_cost(state, action, state_cur, error_func, penalty_func, bbox)
+            raise NotImplementedError(f"{who}: the per-cloud terms come from the device call (no autograd, no CPU tensors)")
+        if n_chunk is None:
+            return running_cost(state, action, state_cur, error_func, penalty_func, bbox)
+        if n_chunk < 1 or state.shape[0] % n_chunk:
+            raise ValueError(f"{who}: {state.shape[0]} samples are not {n_chunk} chunks of equal size")
+        parts = [running_cost(s, a, state_cur, error_func, penalty_func, bbox)["reward_seqs"]
+                 for s, a in zip(state.chunk(n_chunk), action.chunk(n_chunk))]
+        return {"reward_seqs": torch.cat(parts)}
     dev = state.device
     bsz, L, n = state.shape[0], state.shape[1], state.shape[2]
     assert state.dim() == 4 and state.shape[3] == 3 and action.shape[:2] == (bsz, L) and action.shape[2] >= (3 if penalty == "granular" else 2)
@@ -83,11 +95,25 @@ def running_cost_fused(state, action, state_cur, bbox, penalty, sim_real_ratio=1
     terms = torch.empty((bsz, L, _lib.AG_PLAN_TERMS), dtype=torch.float32, device=dev) if return_terms else None
     nbytes = _lib.lib().ag_plan_cost_workspace_bytes(ctypes.byref(prm))
     ws = _lib.workspace(dev, nbytes)
-    _lib.call("ag_plan_cost", dev, ctypes.byref(prm), state, act, init, error, reward, terms, ws, nbytes)
+    if n_chunk is None:
+        _lib.call("ag_plan_cost", dev, ctypes.byref(prm), state, act, init, error, reward, terms, ws, nbytes)
+    else:
+        _lib.call("ag_plan_cost_chunked", dev, ctypes.byref(prm), int(n_chunk), state, act, init, error, reward, terms, ws, nbytes)
     res = {"reward_seqs": reward}
     if return_terms:
         res["terms"] = terms
     return res
+
+
+def running_cost_chunked(state, action, state_cur, n_chunk, bbox, penalty, sim_real_ratio=10.0, error_func=None, box_target=None,
+                         return_terms=False, **kwargs):
+    """The cost of ALL chunks of a planning step (plan.py:241-247 scores each chunk in a `running_cost` call of its own) as one device call,
+    `ag_plan_cost_chunked`: the arguments of `running_cost_fused` plus n_chunk, state (n_chunk * S, L, n, 3) holding chunk c in rows
+    [c S, (c + 1) S).  The error normaliser `2 / (error.max() + 1e-6)` and cloth's largest capped distance are taken over each chunk alone, so
+    reward[c S:(c + 1) S] is bit for bit `running_cost_fused` on that slice (n_chunk = the batch size: every sample its own normaliser, the
+    reference's call on the one best sequence).  `error_func` sees all clouds at once and must score each cloud on its own, as the chamfer and
+    box criteria do.  On CPU tensors and under autograd: the concatenation of `running_cost` over the chunk slices."""
+    return _fused_cost("running_cost_chunked", state, action, state_cur, n_chunk, bbox, penalty, sim_real_ratio, error_func, box_target, return_terms)
 
 
 class Planner:
@@ -196,6 +222,73 @@ class Planner:
                 "best_model_output": best["best_model_output"], "best_eval_output": best["best_eval_output"]}
 
 
+class ChunkedPlanner(Planner):
+    """The chunk loop of plan.py:241-247 — one `Planner.trajectory_optimization` per chunk of n_sample samples, then `merge_res` — as ONE pass
+    over all chunks: per iteration one rollout of n_chunk * n_sample samples, one `running_cost_chunked`, one `optimize_action_mppi_chunks`;
+    afterwards one rollout of the n_chunk best sequences, scored with chunk size 1 (each its own normaliser, the loop's bsz = 1 call), and a
+    device arg-max.  Every chunk keeps its own normalisers, softmax update and best sample, so the results are the loop's; nothing is read back
+    to the host beyond what `model_rollout_fn` reads.
+
+    config: `Planner`'s keys (n_sample is the size of ONE chunk, as plan.py:197 sets it) plus
+      n_chunk      number of chunks
+      cost         dict of `running_cost_chunked`'s keywords: bbox, penalty, and sim_real_ratio, error_func or box_target as needed
+      push_length  of the task (plan_utils.py's codec)
+    Not read, so that the dict of plan.py:188-208 can be passed as it is: evaluate_traj_fn, optimize_action_mppi_fn, clip_action_seq_fn and the
+    per-chunk sampling_action_seq_fn.  The cost and the update are the two device calls with the config's reward_weight and limits; the sampler is
+    `plan_utils.sample_action_seq_chunks` with the config's limits and noise_level (see there for the draw order with n_update_iter > 1).
+
+    `trajectory_optimization(state_cur, act_seq, samples=None)`: act_seq (L, 4), every chunk starts from it.  Returns `merge_res`'s dict plus
+    "chunks": {"act_seq" (C, L, 4), "reward" (C,): every chunk's best sample and its reward in its sampled batch; "new_seqs": the
+    (C, L, 4) MPPI mean of every iteration; "best_reward_seqs" (C,): the rewards of the best sequences rolled out again}.  `samples`, a list
+    of one (C * S, L, 4) tensor per iteration, replaces the sampler (tests, replay)."""
+
+    def __init__(self, config):
+        cost = dict(config["cost"])
+        super().__init__(dict(config, evaluate_traj_fn=functools.partial(running_cost_chunked, **cost)))
+        self.n_chunk, self.push_length = int(config["n_chunk"]), float(config["push_length"])
+        assert self.planner_type == "MPPI" and self.action_dim == 4 and self.rollout_best and self.n_chunk >= 1
+        # the update's limits travel in its parameter block: host copies, made once
+        self.lim_lo, self.lim_hi = self.action_lower_lim.detach().cpu(), self.action_upper_lim.detach().cpu()
+
+    def sample_chunks(self, act_seq, iter_index=0):
+        return sample_action_seq_chunks(act_seq, self.action_lower_lim, self.action_upper_lim, self.n_sample, self.device,
+                                        iter_index=iter_index, noise_level=self.noise_level, push_length=self.push_length)
+
+    @torch.no_grad()
+    def trajectory_optimization(self, state_cur, act_seq, samples=None):
+        C, S, L = self.n_chunk, self.n_sample, self.n_look_ahead
+        assert isinstance(state_cur, torch.Tensor) and isinstance(act_seq, torch.Tensor) and act_seq.shape == (L, 4)
+        assert samples is None or len(samples) == self.n_update_iter
+        act_seq = act_seq[None].repeat(C, 1, 1)
+        model_outputs, eval_outputs, new_seqs = [], [], []
+        best_seq = best_reward = None
+        for i in range(self.n_update_iter):
+            act_seqs = (self.sample_chunks(act_seq, iter_index=i) if samples is None else samples[i]).reshape(C * S, L, 4)
+            model_out = self.model_rollout(state_cur, act_seqs)
+            eval_out = self.evaluate_traj(model_out["state_seqs"], act_seqs, state_cur=state_cur, n_chunk=C)
+            act_seq, _, seq_k, reward_k = optimize_action_mppi_chunks(
+                act_seqs.reshape(C, S, L, 4), eval_out["reward_seqs"].reshape(C, S), reward_weight=self.reward_weight,
+                action_lower_lim=self.lim_lo, action_upper_lim=self.lim_hi, push_length=self.push_length)
+            new_seqs.append(act_seq)
+            if i == 0:
+                best_seq, best_reward = seq_k, reward_k
+            else:                                   # per chunk, the better of the two without reading the comparison back
+                better = reward_k > best_reward
+                best_seq, best_reward = torch.where(better[:, None, None], seq_k, best_seq), torch.where(better, reward_k, best_reward)
+            if self.verbose:
+                model_outputs.append(model_out)
+                eval_outputs.append(eval_out)
+        best_model_out = self.model_rollout(state_cur, best_seq)
+        again = self.evaluate_traj(best_model_out["state_seqs"], best_seq, state_cur=state_cur, n_chunk=C)["reward_seqs"]
+        k = torch.argmax(again).reshape(1)          # merge_res: the chunk whose best sequence scores highest, picked on the device
+        pick = lambda v: v.index_select(0, k) if isinstance(v, torch.Tensor) and v.dim() >= 1 and v.shape[0] == C else v
+        return {"act_seq": best_seq.index_select(0, k)[0], "model_outputs": model_outputs if self.verbose else None,
+                "eval_outputs": eval_outputs if self.verbose else None,
+                "best_model_output": {key: pick(v) for key, v in best_model_out.items()},
+                "best_eval_output": {"reward_seqs": again.index_select(0, k)},
+                "chunks": {"act_seq": best_seq, "reward": best_reward, "new_seqs": new_seqs, "best_reward_seqs": again}}
+
+
 class GradientPlanner(Planner):
     """The reference Planner's 'GD' branch (src/planning/real_world/planner.py:212-223, 279-310): Adam on the sampled action sequences
     themselves, `-mean(reward)` differentiated through the rollout and the cost.  The same config keys as `Planner` (planner_type is not
@@ -265,7 +358,7 @@ class MPPIPlanner:
         self.n_sample_chunk = n_sample_chunk      # None: all samples in ONE rollout (the engine has no memory reason to chunk).  An int only
                                                    # chunks the ROLLOUT's memory: cost normaliser and softmax update still see all samples at once.
                                                    # The reference's chunked planner (rope.yaml:41-42: 20 000 in chunks of 500) is different: an
-                                                   # independent Planner per chunk + merge_res — use mpc.Planner per chunk for those semantics.
+                                                   # independent Planner per chunk + merge_res — mpc.ChunkedPlanner has those semantics.
         # copy=False (multi-GPU): a gathered result is a view of the cached receive buffer, valid until the next gather of the same shape —
         # fine for one rollout scored right away, not for chunked rollouts that are concatenated afterwards
         self.model_rollout = lambda state, acts, copy=True: dynamics_sharded(dynamics, state, acts, model, device, ppm_optimizer, copy=copy)

@@ -339,6 +339,41 @@ size_t ag_plan_cost_workspace_bytes(const ag_plan_cost_params *p);
 int ag_plan_cost(const ag_plan_cost_params *p, const float *state_seqs, const float *action, const float *state_init,
                  const float *error_in, float *reward, float *terms, void *ws, size_t ws_bytes, ag_stream_t stream);
 
+/* ---- a planning step of the reference's chunks in one pass: src/planning/plan.py:180-247 splits n_sample into n_chunk chunks of n_sample_chunk
+ * samples and runs one Planner.trajectory_optimization (src/planning/real_world/planner.py:234-277) per chunk, each with its own cost
+ * normalisers, softmax update and best sample, and merge_res (planner.py:312-323) keeps the best chunk.  The two calls below score and update
+ * all chunks of one rollout of n_chunk S samples, chunk c being samples [c S, (c + 1) S).
+ *
+ * ag_plan_cost_chunked: ag_plan_cost with p->B = n_chunk S (S >= 1; AG_ERR_ARG otherwise), except that "max over all (b, l)" of the error and
+ * of cloth's f is taken over the (b, l) of the sample's own chunk (plan.py:37 and losses.py:61 inside one chunk's call): reward[c S .. (c + 1) S)
+ * holds the bits of ag_plan_cost on that slice of the inputs alone, a NaN error makes the rewards of its chunk NaN and of no other, and
+ * n_chunk = 1 is ag_plan_cost.  Same terms table, same workspace (ag_plan_cost_workspace_bytes(p)), same two launches, the second with one
+ * workgroup per chunk.  No host synchronisation, no memset, no atomics. ---- */
+int ag_plan_cost_chunked(const ag_plan_cost_params *p, int n_chunk, const float *state_seqs, const float *action, const float *state_init,
+                         const float *error_in, float *reward, float *terms, void *ws, size_t ws_bytes, ag_stream_t stream);
+
+/* optimize_action_mppi and clip_actions of src/planning/plan_utils.py:31-39 and 80-101 for every chunk, and the arg-max of planner.py:259-265, in one
+ * launch of one workgroup per chunk.  actions (n_chunk S, L, 4) = (x, z, theta, length), reward (n_chunk S), fp32.  Per chunk, every product and
+ * sum rounded separately and every reduction in one fixed order (the same bits on every call):
+ *   w = softmax(reward reward_weight) over the chunk's S samples, the largest exponent subtracted; S = 1 gives the weight 1 exactly
+ *   per look-ahead index l the sums over the samples of w x, w z, w x_end, w z_end,
+ *     x_end = x - (length push_length) cos theta,  z_end = z - (length push_length) sin theta
+ *   theta' = atan2(z - z_end, x - x_end) of the sums, wrapped by ((theta' + pi) mod 2 pi) - pi with the divisor's sign (pi as a float)
+ *   length' = sqrt(dx dx + dz dz) / push_length,  (dx, dz) = the summed end minus the summed start
+ *   new_seq[c, l] = (x, z, theta', length') clamped to [lo, hi] per field: min with hi, then max with lo, a NaN kept
+ *   best_idx[c] = the index inside the chunk of its largest reward: the lowest index on ties, and a NaN reward counts as the largest, the first
+ *     NaN winning (torch.argmax, np.argmax); best_seq[c] = that sample's (L, 4) rows, best_reward[c] = its reward, both copied bit for bit
+ * A NaN reward makes new_seq of its chunk NaN and of no other.  Out: new_seq (n_chunk, L, 4), best_idx (n_chunk) int32, best_seq (n_chunk, L, 4),
+ * best_reward (n_chunk); any of them may be NULL.  n_chunk, S, L >= 1 and n_chunk S L <= 2^30 (AG_ERR_ARG otherwise).  No scratch, no host
+ * synchronisation, no atomics: capturable in a HIP graph. */
+typedef struct ag_mppi_params {
+    int n_chunk, S, L;
+    float reward_weight, push_length;
+    float lo[4], hi[4];    /* action limits per field (x, z, theta, length) */
+} ag_mppi_params;
+int ag_mppi_update(const ag_mppi_params *p, const float *actions, const float *reward, float *new_seq, int32_t *best_idx, float *best_seq,
+                   float *best_reward, ag_stream_t stream);
+
 /* ---- farthest-point key-point sampling (SURVEY.md §8f row n3 data side): the two passes of fps() of src/dynamics/dataset/graph.py:8-36 — the
  * first is dgl.geometry.farthest_point_sampler, the second fps_rad_idx of src/dynamics/utils.py:10-24 — and with them the perception step of
  * the closed loop, src/planning/perception.py:266-279.  B clouds in one launch, one workgroup per cloud.
