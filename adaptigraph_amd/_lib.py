@@ -20,6 +20,8 @@ KERNEL_CLASSES = ("build_edges", "node_encode", "edge_encode", "aggregate", "nod
 
 AG_VARIANT_SINGLE, AG_VARIANT_BATCH = 0, 1
 AG_HEIGHT_MIN, AG_HEIGHT_MASKED_MEAN = 0, 1
+AG_RAGGED_MAX_STEPS = 1024
+AG_STATUS_NONFINITE, AG_STATUS_ORDER = 1, 4
 AG_PENALTIES = {None: 0, "rope": 1, "cloth": 2, "granular": 3}      # AG_PENALTY_*
 AG_ERROR_GIVEN, AG_ERROR_BOX = 0, 1
 AG_PLAN_TERMS = 9
@@ -97,6 +99,9 @@ SIGNATURES = {
     # scripted rollout
     "ag_rollout_scripted_workspace_bytes_for": (c_size_t, [c_void_p, P(ScriptedParams)]),
     "ag_rollout_scripted": (c_int, [c_void_p, P(ScriptedParams)] + [c_void_p] * 16 + [c_size_t, c_void_p]),
+    # ragged rollout
+    "ag_rollout_order": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "ag_rollout_ragged": (c_int, [c_void_p, P(RolloutParams)] + [c_void_p] * 10 + [P(c_int32)] + [c_void_p] * 4 + [c_size_t, c_void_p]),
     # chamfer, both clouds resident in LDS
     "ag_chamfer": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2),
     "ag_chamfer_masked": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 2),

@@ -481,8 +481,22 @@ struct AgStepArgs {
     float *out_seq;           // (B, n_p, 3) recorded when repeat == step
     int B, N, n_p, H, step, height_mode;
     float raise;              // gripper raise (0 when disabled)
+    // ragged rollout (ag_rollout_ragged): sample b records into row out_index[b] of out_seq instead of row b; an index outside [0, out_rows) raises
+    // AG_STATUS_ORDER in *status and records nothing.  NULL: row b (every other driver)
+    const int32_t *out_index;
+    int out_rows;
+    int *status;
 };
 void ag_launch_rollout_step(const AgStepArgs &a, hipStream_t s);
+// Ragged rollout, behind the last step: state_final[out_index ? out_index[b] : b] = state[b] for the B samples of `state` (B, H, N, 3) — a sample's history
+// stands still from its own last step on — and the call's device checks: repeat (B) in non-increasing order (negatives as 0), every out_index in
+// [0, B); a failed check raises AG_STATUS_ORDER in *status, and an out-of-range row is not written.  state_final may be NULL (checks only).
+#define AG_STATUS_ORDER_BIT 4
+void ag_launch_ragged_finish(const float *state, const int32_t *repeat, const int32_t *out_index, float *state_final, int B, int H, int N, int *status,
+                             hipStream_t s);
+// ag_order.hip: order (B) = the samples by non-increasing repeat, ties by ascending index; active (AG_ORDER_STEPS + 1): samples with repeat >= s + 1
+#define AG_ORDER_STEPS 1024
+void ag_launch_rollout_order(const int32_t *repeat, int B, int32_t *order, int32_t *active, hipStream_t s);
 void ag_launch_zero_words(int32_t *p, int n, hipStream_t s);      // (a kernel, not a memset node: HIP-graph replay)
 
 // Scripted rollout (ag_scripted.hip): the state update behind the forward of step t, tool slots = the last N - n_p of a sample

@@ -1,6 +1,9 @@
-// ag_drivers.hip — the three rollout drivers of the C ABI: ag_rollout (round-robin or CU-partitioned scheduler), its shared-state form, and
-// ag_rollout_scripted; each carves its lanes, binds a step's arguments once and runs the engine's kernel sequence (ag_engine.hip) per model step.
+// ag_drivers.hip — the rollout drivers of the C ABI: ag_rollout (round-robin or CU-partitioned scheduler), its shared-state form, ag_rollout_ragged
+// (either form on one stream, every model step sized for the samples still running) and ag_rollout_scripted; each carves its lanes, binds a step's
+// arguments once and runs the engine's kernel sequence (ag_engine.hip) per model step.
 #include "ag_host.h"
+
+static_assert(AG_ORDER_STEPS == AG_RAGGED_MAX_STEPS && AG_STATUS_ORDER_BIT == AG_STATUS_ORDER, "the kernels' constants are the header's");
 
 namespace {
 
@@ -12,6 +15,13 @@ struct Lane {   // what a rollout driver keeps per batch part [b0, b0 + B) (the 
     float *state = nullptr, *pred_pos = nullptr, *pred_motion = nullptr;
     hipStream_t s = nullptr;
     int b0 = 0, B = 0;
+};
+
+// ag_rollout_ragged: the samples are in non-increasing order of `repeat`, so the samples that still run at model step ai are the first active[ai - 1]
+// (a HOST array) and every launch of that step is sized for them; table bases and row numbers stay those of the whole batch.  A sample records into row
+// out_index[b] (device array; NULL: b) of out_seq and state_final
+struct Ragged {
+    const int32_t *active, *out_index;
 };
 
 // One step's buffers of a lane of B samples (Params: ag_rollout_params or ag_scripted_params): predictions of pred_n slots per sample, the lists the edge
@@ -96,6 +106,44 @@ static void carve_parts(Carver &c, const ag_model *m, const ag_rollout_params *p
     }
 }
 
+struct RolloutIn {   // the ten input arrays of an ag_rollout call, whole batch
+    const float *state0, *delta, *attrs, *p_instance, *phys;
+    const uint8_t *mask, *tool_mask, *obj_mask;
+    const float *thr_sq;
+    const int32_t *repeat;
+};
+
+// A part's arguments from its carving, its stream and its slice of the batch (nothing is enqueued here).  `partitioned`: the CU-partitioned scheduler
+static void bind_part(ag_model *m, const ag_rollout_params *p, Lane &l, const RolloutIn &in, float *out_seq, bool partitioned, int part_blocks)
+{
+    const int H = m->cfg.n_his, N = p->N, n_p = p->n_p, Pd = m->cfg.phys_dim;
+    const size_t plane = (size_t)N * 3, b0 = (size_t)l.b0;
+    AgEdgeArgs &e = l.e;
+    AgFwdArgs &f = l.f;
+    bind_edges(l, p, AG_VARIANT_BATCH, H, in.mask + b0 * N, in.tool_mask + b0 * N, in.thr_sq + b0);
+    bind_forward(m, f, l.B, N, n_p, p->n_instance, l.state, in.attrs + b0 * N * 2, in.delta + b0 * plane, in.p_instance + b0 * n_p * p->n_instance,
+                 in.phys ? in.phys + b0 * Pd : nullptr, e.row_ptr, e.edge_recv, e.edge_send, l.pred_pos, l.pred_motion);
+    if (m->self_edges) {      // self-edge elision: the builder leaves class-0 / class-1 self-loops out of the lists, the encoder adds one row per class
+        e.self_attrs = f.attrs; e.self_class_row0 = f.self_class_row0;
+        f.self_info = e.self_info; f.self_rows = AG_SELF_ROWS;
+    }
+    if (partitioned) {
+        setup_args(m, f, l.path, AG_MLP_WG_PER_CU * (m->n_cus - m->cu_split));   // persistent node kernels: the HBM partition's CUs
+        f.ws_blocks = m->cu_split;                                                // edge encoder: one workgroup per CU of the MFMA partition
+    } else {
+        setup_args(m, f, l.path, part_blocks);
+        // riders of the edge builder's launches (one 15 us launch per model step less each): the edge encoder's per-node input rows and, for a
+        // de-duplicated node encoder, the sender column mapped to compact rows
+        wire_tab_rider(l);
+        if (f.dedup) { e.map_node_row = f.node_row; e.map_ovf = f.ovf; e.map_send_c = f.send_c; }
+    }
+    AgStepArgs &st = l.st;
+    st.state = l.state; st.delta = in.delta + b0 * plane; st.pred_pos = l.pred_pos;
+    st.obj_mask = in.obj_mask ? in.obj_mask + b0 * n_p : nullptr; st.repeat = in.repeat + b0;
+    st.out_seq = out_seq + b0 * n_p * 3; st.B = l.B; st.N = N; st.n_p = n_p; st.H = H;
+    st.height_mode = p->height_mode; st.raise = p->gripper_raise;
+}
+
 // The two CU-masked streams of the partitioned rollout (created once per cu_split value).  Mask bit b is CU slot b / 8 of XCD b % 8
 // (tools/ubench/cu_mask_map.hip -> profiles/r05_cu_mask_map.txt), so bits [0, X) and [X, n_cus) with X a multiple of 8 are disjoint sets of
 // X / 8 and (n_cus - X) / 8 CUs of EVERY XCD: both partitions keep all eight L2s and all memory channels.
@@ -168,7 +216,7 @@ static void carve_shared(Carver &c, const ag_model *m, const ag_rollout_params *
 static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *state0, const float *delta, const float *attrs,
                           const float *p_instance, const float *phys, const uint8_t *mask, const uint8_t *tool_mask, const uint8_t *obj_mask,
                           const float *thr_sq, const int32_t *repeat, float *out_seq, float *state_final, void *workspace, size_t workspace_bytes,
-                          hipStream_t s)
+                          hipStream_t s, const Ragged *rg = nullptr)
 {
     Lane l;
     l.path = resolve_path(m, p->B + 1, p->N, p->n_instance, p->n_steps, true);
@@ -205,7 +253,12 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
     st.state = sh.s_state; st.delta = sh.s_delta; st.pred_pos = l.pred_pos; st.obj_mask = obj_mask ? sh.s_obj_mask : nullptr;
     st.repeat = sh.s_repeat; st.out_seq = out_seq; st.B = B1; st.N = N; st.n_p = n_p; st.H = H;
     st.height_mode = p->height_mode; st.raise = p->gripper_raise; st.cmap = sh.cmap; st.dirty = sh.dirty; st.sample_dirty = sh.sample_dirty;
+    if (rg) { st.out_index = rg->out_index; st.out_rows = p->B; st.status = m->status; }
     for (int ai = 1; ai <= p->n_steps; ++ai) {
+        if (rg) {      // the base and the samples still running: internal samples [0, 1 + active)
+            if (rg->active[ai - 1] < 1) break;
+            sh.B1 = e.B = fE.B = fP.B = st.B = 1 + rg->active[ai - 1];
+        }
         int riders;
         { Timed tm(m, AG_K_EDGES, s); ag_launch_shared_active(sh, s); riders = ag_launch_build_edges(e, s); ag_launch_shared_compact(sh, s); }
         fE.tab_done = (riders & AG_RIDER_TAB) != 0;
@@ -214,7 +267,8 @@ static int rollout_shared(ag_model *m, const ag_rollout_params *p, const float *
         st.step = ai;
         { Timed tm(m, AG_K_ROLLOUT_STEP, s); ag_launch_rollout_step(st, s); }
     }
-    if (state_final)
+    if (rg) ag_launch_ragged_finish(sh.s_state + (size_t)H * plane, repeat, rg->out_index, state_final, p->B, H, N, m->status, s);
+    else if (state_final)
         AG_HIP(hipMemcpyAsync(state_final, sh.s_state + (size_t)H * plane, (size_t)p->B * H * plane * sizeof(float), hipMemcpyDeviceToDevice, s));
     AG_HIP(hipGetLastError());
     return AG_OK;
@@ -269,30 +323,39 @@ struct Join {   // RAII: whichever way ag_rollout returns, the streams it forked
     ~Join() { (void)join(); }
 };
 
+// Model step ai of a lane on its own stream, in two halves: the step's graph up to the edge encoder, then the propagation rounds and the state step
+static void step_graph(ag_model *m, Lane &l, int ai)
+{
+    AgFwdArgs &f = l.f;
+    // (step-invariant when de-duplicated, see run_node_encode; in front of the edge build, whose sender-map rider needs its node_row)
+    if (ai == 1 || !f.dedup) run_node_encode(m, f, l.s);
+    int riders;
+    { Timed tm(m, AG_K_EDGES, l.s); riders = ag_launch_build_edges(l.e, l.s); }
+    f.tab_done = (riders & AG_RIDER_TAB) != 0;
+    f.remap_done = (riders & AG_RIDER_MAP) != 0;
+    run_node_encode_fallback(m, f, l.s);
+    run_edge_encode(m, f, l.path, l.s);
+}
+static void step_rounds(ag_model *m, Lane &l, int ai)
+{
+    run_propagate(m, l.f, l.path, l.s);
+    l.st.step = ai;
+    { Timed tm(m, AG_K_ROLLOUT_STEP, l.s); ag_launch_rollout_step(l.st, l.s); }
+}
+
 // One stream per part, the steps issued round-robin over the parts so every stream always has work queued
 static int issue_round_robin(ag_model *m, hipStream_t s0, Lane *lane, int parts, int n_steps)
 {
     for (int ai = 1; ai <= n_steps; ++ai)
         for (int k = 0; k < parts; ++k) {
-            Lane &l = lane[k];
-            AgFwdArgs &f = l.f;
-            // (step-invariant when de-duplicated, see run_node_encode; in front of the edge build, whose sender-map rider needs its node_row)
-            if (ai == 1 || !f.dedup) run_node_encode(m, f, l.s);
-            int riders;
-            { Timed tm(m, AG_K_EDGES, l.s); riders = ag_launch_build_edges(l.e, l.s); }
-            f.tab_done = (riders & AG_RIDER_TAB) != 0;
-            f.remap_done = (riders & AG_RIDER_MAP) != 0;
-            run_node_encode_fallback(m, f, l.s);
-            run_edge_encode(m, f, l.path, l.s);
+            step_graph(m, lane[k], ai);
             if (ai == 1 && k == 0 && parts > 1) {
                 // phase offset: the other parts start once part 0 has finished its first MFMA-bound encode stage, so
                 // from then on one stream's HBM-bound segment reduce co-runs with another stream's MFMA-bound stage
                 AG_HIP(hipEventRecord(m->ev_fork, s0));
                 for (int kk = 1; kk < parts; ++kk) AG_HIP(hipStreamWaitEvent(m->aux_stream[kk], m->ev_fork, 0));
             }
-            run_propagate(m, f, l.path, l.s);
-            l.st.step = ai;
-            { Timed tm(m, AG_K_ROLLOUT_STEP, l.s); ag_launch_rollout_step(l.st, l.s); }
+            step_rounds(m, lane[k], ai);
         }
     return AG_OK;
 }
@@ -333,23 +396,31 @@ static int issue_partitioned(ag_model *m, Lane *lane, int parts, int n_steps)
     return AG_OK;
 }
 
+// The argument checks ag_rollout and ag_rollout_ragged share, up to the first read of the model (`who`: the entry point, for the message)
+static int rollout_args_ok(const char *who, const ag_model *m, const ag_rollout_params *p, const RolloutIn &in, const float *out_seq, const void *workspace)
+{
+    if (!m || !p || !in.state0 || !in.delta || !in.attrs || (!in.p_instance && p->n_instance > 0) || !in.mask || !in.tool_mask || !in.thr_sq ||
+        !in.repeat || !out_seq || !workspace)
+        return ag_fail(AG_ERR_ARG, "%s: null argument", who);
+    if (p->height_mode == AG_HEIGHT_MASKED_MEAN && !in.obj_mask) return ag_fail(AG_ERR_ARG, "%s: obj_mask is null", who);
+    if (p->B < 1 || p->N < 1 || p->n_p < 1 || p->n_p > p->N || p->topk < 1 || p->topk > 64 || p->n_steps < 0)
+        return ag_fail(AG_ERR_ARG, "%s: bad sizes", who);
+    return AG_OK;
+}
+
 int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, const float *delta, const float *attrs,
                const float *p_instance, const float *phys, const uint8_t *mask, const uint8_t *tool_mask,
                const uint8_t *obj_mask, const float *thr_sq, const int32_t *repeat, float *out_seq,
                float *state_final, void *workspace, size_t workspace_bytes, ag_stream_t stream)
 {
-    if (!m || !p || !state0 || !delta || !attrs || (!p_instance && p->n_instance > 0) || !mask || !tool_mask || !thr_sq || !repeat ||
-        !out_seq || !workspace)
-        return ag_fail(AG_ERR_ARG, "ag_rollout: null argument");
-    if (p->height_mode == AG_HEIGHT_MASKED_MEAN && !obj_mask) return ag_fail(AG_ERR_ARG, "ag_rollout: obj_mask is null");
-    if (p->B < 1 || p->N < 1 || p->n_p < 1 || p->n_p > p->N || p->topk < 1 || p->topk > 64 || p->n_steps < 0)
-        return ag_fail(AG_ERR_ARG, "ag_rollout: bad sizes");
+    const RolloutIn in{state0, delta, attrs, p_instance, phys, mask, tool_mask, obj_mask, thr_sq, repeat};
+    if (int rc = rollout_args_ok("ag_rollout", m, p, in, out_seq, workspace)) return rc;
     if (m->cfg.phys_dim > 0 && !phys) return ag_fail(AG_ERR_ARG, "ag_rollout: phys is null");
     hipStream_t s0 = static_cast<hipStream_t>(stream);
     if (shared_applicable(m, p))
         return rollout_shared(m, p, state0, delta, attrs, p_instance, phys, mask, tool_mask, obj_mask, thr_sq, repeat, out_seq, state_final, workspace,
                               workspace_bytes, s0);
-    const int H = m->cfg.n_his, N = p->N, n_p = p->n_p, Pd = m->cfg.phys_dim;
+    const int H = m->cfg.n_his, N = p->N;
     const int parts = rollout_parts(p->B, rollout_want(m, p));
     for (int k = 1; k < parts; ++k)
         if (!m->aux_stream[k]) {
@@ -368,33 +439,8 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
     const size_t plane = (size_t)N * 3;
     const int part_blocks = m->max_blocks / parts > 0 ? m->max_blocks / parts : 1;   // each part's persistent kernels take an equal share
     for (int k = 0; k < parts; ++k) {      // the parts' arguments (nothing is enqueued here)
-        Lane &l = lane[k];
-        AgEdgeArgs &e = l.e;
-        AgFwdArgs &f = l.f;
-        const size_t b0 = (size_t)l.b0;
-        l.s = partitioned ? m->hbm_stream : (k == 0 ? s0 : m->aux_stream[k]);
-        bind_edges(l, p, AG_VARIANT_BATCH, H, mask + b0 * N, tool_mask + b0 * N, thr_sq + b0);
-        bind_forward(m, f, l.B, N, n_p, p->n_instance, l.state, attrs + b0 * N * 2, delta + b0 * plane, p_instance + b0 * n_p * p->n_instance,
-                     phys ? phys + b0 * Pd : nullptr, e.row_ptr, e.edge_recv, e.edge_send, l.pred_pos, l.pred_motion);
-        if (m->self_edges) {      // self-edge elision: the builder leaves class-0 / class-1 self-loops out of the lists, the encoder adds one row per class
-            e.self_attrs = f.attrs; e.self_class_row0 = f.self_class_row0;
-            f.self_info = e.self_info; f.self_rows = AG_SELF_ROWS;
-        }
-        if (partitioned) {
-            setup_args(m, f, l.path, AG_MLP_WG_PER_CU * (m->n_cus - m->cu_split));   // persistent node kernels: the HBM partition's CUs
-            f.ws_blocks = m->cu_split;                                                // edge encoder: one workgroup per CU of the MFMA partition
-        } else {
-            setup_args(m, f, l.path, part_blocks);
-            // riders of the edge builder's launches (one 15 us launch per model step less each): the edge encoder's per-node input rows and, for a
-            // de-duplicated node encoder, the sender column mapped to compact rows
-            wire_tab_rider(l);
-            if (f.dedup) { e.map_node_row = f.node_row; e.map_ovf = f.ovf; e.map_send_c = f.send_c; }
-        }
-        AgStepArgs &st = l.st;
-        st.state = l.state; st.delta = delta + b0 * plane; st.pred_pos = l.pred_pos;
-        st.obj_mask = obj_mask ? obj_mask + b0 * n_p : nullptr; st.repeat = repeat + b0;
-        st.out_seq = out_seq + b0 * n_p * 3; st.B = l.B; st.N = N; st.n_p = n_p; st.H = H;
-        st.height_mode = p->height_mode; st.raise = p->gripper_raise;
+        lane[k].s = partitioned ? m->hbm_stream : (k == 0 ? s0 : m->aux_stream[k]);
+        bind_part(m, p, lane[k], in, out_seq, partitioned, part_blocks);
     }
     Join join{s0};
     if (parts > 1) AG_HIP(hipEventRecord(m->ev_fork, s0));
@@ -411,6 +457,56 @@ int ag_rollout(ag_model *m, const ag_rollout_params *p, const float *state0, con
     for (const Lane *l = lane; l < lane + parts && state_final; ++l)
         AG_HIP(hipMemcpyAsync(state_final + (size_t)l->b0 * H * plane, l->state, (size_t)l->B * H * plane * sizeof(float), hipMemcpyDeviceToDevice, l->s));
     AG_HIP(join.join());
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_rollout_order(const int32_t *repeat, int B, int32_t *order, int32_t *active, ag_stream_t stream)
+{
+    if (!repeat || !order || !active) return ag_fail(AG_ERR_ARG, "ag_rollout_order: null argument");
+    if (B < 1) return ag_fail(AG_ERR_ARG, "ag_rollout_order: B=%d (>= 1)", B);
+    ag_launch_rollout_order(repeat, B, order, active, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+// ag_rollout on a batch in the order of ag_rollout_order, one stream: the plain driver as ONE part, or the shared-state driver, with every launch of
+// model step ai sized for the first active_per_step[ai - 1] samples.  A retired sample's rows are never touched again: its history stands still at its
+// own last step (state_final), and nothing it would have computed later is recorded anywhere (forward_dynamics.py:160-161).
+int ag_rollout_ragged(ag_model *m, const ag_rollout_params *p, const float *state0, const float *delta, const float *attrs, const float *p_instance,
+                      const float *phys, const uint8_t *mask, const uint8_t *tool_mask, const uint8_t *obj_mask, const float *thr_sq,
+                      const int32_t *repeat, const int32_t *active_per_step, const int32_t *out_index, float *out_seq, float *state_final,
+                      void *workspace, size_t workspace_bytes, ag_stream_t stream)
+{
+    const RolloutIn in{state0, delta, attrs, p_instance, phys, mask, tool_mask, obj_mask, thr_sq, repeat};
+    if (int rc = rollout_args_ok("ag_rollout_ragged", m, p, in, out_seq, workspace)) return rc;
+    // (the step counts are checked before the model is read)
+    if (p->n_steps > AG_RAGGED_MAX_STEPS) return ag_fail(AG_ERR_ARG, "ag_rollout_ragged: n_steps=%d (<= %d)", p->n_steps, AG_RAGGED_MAX_STEPS);
+    if (!active_per_step && p->n_steps > 0) return ag_fail(AG_ERR_ARG, "ag_rollout_ragged: null argument (active_per_step)");
+    for (int ai = 0; ai < p->n_steps; ++ai)
+        if (active_per_step[ai] < 0 || active_per_step[ai] > (ai > 0 ? active_per_step[ai - 1] : p->B))
+            return ag_fail(AG_ERR_ARG, "ag_rollout_ragged: active_per_step[%d]=%d (non-increasing, 0..B=%d)", ai, active_per_step[ai], p->B);
+    if (m->cfg.phys_dim > 0 && !phys) return ag_fail(AG_ERR_ARG, "ag_rollout_ragged: phys is null");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const Ragged rg{active_per_step, out_index};
+    if (shared_applicable(m, p))
+        return rollout_shared(m, p, state0, delta, attrs, p_instance, phys, mask, tool_mask, obj_mask, thr_sq, repeat, out_seq, state_final, workspace,
+                              workspace_bytes, s, &rg);
+    Lane l;
+    Carver c(workspace, workspace_bytes);
+    carve_parts(c, m, p, 1, &l);
+    if (!c.ok()) return ag_fail(AG_ERR_WS, "ag_rollout_ragged: workspace %zu < %zu bytes", workspace_bytes, c.off);
+    l.s = s;
+    bind_part(m, p, l, in, out_seq, false, m->max_blocks);
+    const int H = m->cfg.n_his;
+    l.st.out_index = out_index; l.st.out_rows = p->B; l.st.status = m->status;
+    AG_HIP(hipMemcpyAsync(l.state, state0, (size_t)p->B * H * p->N * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
+    for (int ai = 1; ai <= p->n_steps && active_per_step[ai - 1] > 0; ++ai) {
+        l.e.B = l.f.B = l.st.B = active_per_step[ai - 1];      // counts and grids shrink; bases and row numbers are the whole batch's
+        step_graph(m, l, ai);
+        step_rounds(m, l, ai);
+    }
+    ag_launch_ragged_finish(l.state, repeat, out_index, state_final, p->B, H, p->N, m->status, s);
     AG_HIP(hipGetLastError());
     return AG_OK;
 }

@@ -54,8 +54,16 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(AgStepArgs a)
     const int plane = a.N * 3;
     const int k0 = blockIdx.y * kStepChunk, k1 = min(k0 + kStepChunk, plane);
     if (a.repeat[b] == a.step && !(SHARED && b == 0)) {
-        float *o = a.out_seq + (size_t)(SHARED ? b - 1 : b) * a.n_p * 3;      // (shared-state rollout: internal sample b is the caller's b - 1; the base records nothing)
-        for (int k = k0 + tid; k < min(k1, a.n_p * 3); k += 256) o[k] = SHARED ? at(k / 3, k % 3) : pred[k];
+        int row = SHARED ? b - 1 : b;      // (shared-state rollout: internal sample b is the caller's b - 1; the base records nothing)
+        bool ok = true;
+        if (a.out_index) {                 // ragged rollout: the caller's row of this sample (uniform over the workgroup)
+            row = a.out_index[row];
+            ok = (unsigned)row < (unsigned)a.out_rows;
+            if (!ok && tid == 0 && blockIdx.y == 0) atomicOr(a.status, AG_STATUS_ORDER_BIT);
+        }
+        float *o = a.out_seq + (size_t)row * a.n_p * 3;
+        if (ok)
+            for (int k = k0 + tid; k < min(k1, a.n_p * 3); k += 256) o[k] = SHARED ? at(k / 3, k % 3) : pred[k];
     }
     float *st = a.state + (size_t)b * a.H * a.N * 3;
     const float *dl = a.delta + (size_t)b * a.N * 3;
@@ -102,7 +110,39 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(AgStepArgs a)
     }
 }
 
+// Ragged rollout, behind the last step (ag_common.h: ag_launch_ragged_finish).  grid (B, chunks of a sample's H N 3 floats)
+__global__ __launch_bounds__(256) void ragged_finish_kernel(const float *state, const int32_t *repeat, const int32_t *out_index, float *state_final,
+                                                           int B, int per, int *status)
+{
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int row = out_index ? out_index[b] : b;
+    const bool ok = (unsigned)row < (unsigned)B;
+    if (tid == 0 && blockIdx.y == 0) {
+        const int r = max(repeat[b], 0), before = b > 0 ? max(repeat[b - 1], 0) : r;
+        if (!ok || before < r) atomicOr(status, AG_STATUS_ORDER_BIT);
+    }
+    if (!ok || !state_final) return;
+    const float *src = state + (size_t)b * per;
+    float *dst = state_final + (size_t)row * per;
+    constexpr int kPer = kStepChunk / 256;
+    const int k0 = blockIdx.y * kStepChunk + tid;
+    float v[kPer];
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) v[i] = k0 + 256 * i < per ? src[k0 + 256 * i] : 0.f;
+#pragma unroll
+    for (int i = 0; i < kPer; ++i)
+        if (k0 + 256 * i < per) dst[k0 + 256 * i] = v[i];
+}
+
 }  // namespace
+
+void ag_launch_ragged_finish(const float *state, const int32_t *repeat, const int32_t *out_index, float *state_final, int B, int H, int N, int *status,
+                             hipStream_t s)
+{
+    const int per = H * N * 3;
+    hipLaunchKernelGGL(ragged_finish_kernel, dim3(B, (per + kStepChunk - 1) / kStepChunk), dim3(256), 0, s, state, repeat, out_index, state_final, B, per,
+                       status);
+}
 
 // Zero a few device words with a KERNEL instead of hipMemsetAsync: inside a captured HIP graph the memset NODES of the shared-state rollout were not
 // reliably replayed (second replay of tests' graph: garbage; eager calls and the first replay fine), kernel nodes are.

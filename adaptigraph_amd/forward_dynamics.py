@@ -19,13 +19,36 @@ from .graph import threshold_sq
 from .plan_utils import decode_action
 
 
+def rollout_order(repeat):
+    """The ordering of a ragged rollout for repeat (B,) int32 -> order (B,) int32, active (AG_RAGGED_MAX_STEPS + 1,) int32, on repeat's device
+    (ag_rollout_order, include/adaptigraph_hip.h): order = the samples by repeat descending (negatives as 0), ties by ascending index;
+    active[s] = #{b : repeat[b] >= s + 1}, the last word = #{b : repeat[b] > AG_RAGGED_MAX_STEPS}.  A GPU tensor takes the library's one launch
+    (no host synchronisation); a CPU tensor the same arithmetic in torch, which is what the kernel is tested against."""
+    S = _lib.AG_RAGGED_MAX_STEPS
+    B = repeat.shape[0]
+    if not repeat.is_cuda:
+        r = repeat.to(torch.int64).clamp_min(0)
+        order = torch.sort(r, descending=True, stable=True).indices.to(torch.int32)
+        hist = torch.bincount(r.clamp_max(S + 1), minlength=S + 2)      # keys 0 .. S, and "above"
+        active = hist.flip(0).cumsum(0).flip(0)[1:].to(torch.int32)     # active[s] = sum of hist[s + 1:]
+        return order, active
+    repeat = repeat.to(torch.int32).contiguous()
+    order = torch.empty(B, dtype=torch.int32, device=repeat.device)
+    active = torch.empty(S + 1, dtype=torch.int32, device=repeat.device)
+    _lib.call("ag_rollout_order", repeat.device, repeat, B, order, active)
+    return order, active
+
+
 def rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr_sq, repeat, n_steps, topk,
             connect_tools_all, max_tools, height_mode=_lib.AG_HEIGHT_MIN, obj_mask=None, gripper_raise=0.0,
-            return_state=False, out=None):
+            return_state=False, out=None, order=None, active=None):
     """Native inner loop (forward_dynamics.py:156-197).  All tensors on the model's GPU.
     state0 (B,H,N,3), delta (B,N,3), attrs (B,N,2), p_instance (B,n_p,I), phys (B,P), mask/tool_mask (B,N) bool,
     thr_sq (B,), repeat (B,) int32 -> out_seq (B,n_p,3): prediction of step repeat[b] (zeros if never reached).
-    `out`: an already ZEROED contiguous fp32 (B,n_p,3) tensor to write into instead of a fresh one."""
+    `out`: an already ZEROED contiguous fp32 (B,n_p,3) tensor to write into instead of a fresh one.
+    `active`: a HOST int32 tensor of at least n_steps words makes this the ragged rollout (ag_rollout_ragged): the inputs are in the order of
+    rollout_order — repeat non-increasing — step s runs the first active[s - 1] samples only, and sample b's result goes to row order[b] (a GPU
+    int32 tensor; None: row b) of the outputs; the returned state is then every sample's history after its OWN last step."""
     L = _lib.lib()
     dev = state0.device
     B, H, N, _ = state0.shape
@@ -47,9 +70,35 @@ def rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr_
     obj_u8 = _u8(obj_mask) if obj_mask is not None else None
     repeat = repeat.to(dev, torch.int32).contiguous()
     thr_sq = thr_sq.contiguous()
-    _lib.call("ag_rollout", dev, h, ctypes.byref(prm), state0, delta, attrs, p_instance, phys, mask_u8, tool_u8, obj_u8, thr_sq, repeat,
-              out_seq, state_final, ws, ws.numel())
+    if active is not None:
+        assert not active.is_cuda and active.dtype == torch.int32 and active.is_contiguous() and active.numel() >= int(n_steps)
+        assert order is None or (order.device == dev and order.dtype == torch.int32 and order.is_contiguous() and order.numel() == B)
+        _lib.call("ag_rollout_ragged", dev, h, ctypes.byref(prm), state0, delta, attrs, p_instance, phys, mask_u8, tool_u8, obj_u8, thr_sq, repeat,
+                  ctypes.cast(active.data_ptr(), ctypes.POINTER(ctypes.c_int32)), order, out_seq, state_final, ws, ws.numel())
+    else:
+        _lib.call("ag_rollout", dev, h, ctypes.byref(prm), state0, delta, attrs, p_instance, phys, mask_u8, tool_u8, obj_u8, thr_sq, repeat,
+                  out_seq, state_final, ws, ws.numel())
     return (out_seq, state_final) if return_state else out_seq
+
+
+def _ragged_plan(rep_cols, device):
+    """The device half of a ragged dynamics() call, enqueued BEFORE its one host read: ag_rollout_order per look-ahead column of rep_cols
+    (n_look, B) int32, and the per-step counts on their way to pinned memory -> orders (n_look, B) on the GPU, the pinned (n_look,
+    AG_RAGGED_MAX_STEPS + 1) counts (valid once the stream has been synchronised)."""
+    n_look, bsz = rep_cols.shape
+    S1 = _lib.AG_RAGGED_MAX_STEPS + 1
+    orders = torch.empty((n_look, bsz), dtype=torch.int32, device=rep_cols.device)
+    actives = torch.empty((n_look, S1), dtype=torch.int32, device=rep_cols.device)
+    for li in range(n_look):
+        _lib.call("ag_rollout_order", rep_cols.device, rep_cols[li], bsz, orders[li], actives[li])
+    host = _pinned(n_look * S1, torch.int32, device).view(n_look, S1)
+    host.copy_(actives, non_blocking=True)
+    return orders, host
+
+
+def _ragged_steps(active):
+    """Model steps of a column from its pinned counts, or None where a sample runs longer than AG_RAGGED_MAX_STEPS (the plain call's case)."""
+    return None if int(active[-1]) != 0 else int(torch.count_nonzero(active[:-1]))
 
 
 def rollout_scripted(model, state0, action0, tool_pos, tool_delta, attrs, p_instance, phys, mask, tool_mask, thr_sq, topk,
@@ -235,18 +284,27 @@ def dynamics(state, action, model, device, ppm_optimizer, physics_param=None):
     obj_still = obj_still.expand(bsz, n_obj, 3)
     phys = _physics(ppm_optimizer, physics_param, bsz, device)
     thr = threshold_sq(ppm_optimizer.adj_thresh, bsz, torch.device(device), _lib.AG_VARIANT_BATCH)
-    rep_max = repeat.max(dim=0).values
+    ragged = bool(getattr(model, "ragged_rollout", False))
+    rep_max = None if ragged else repeat.max(dim=0).values
     rep_cols = repeat.to(torch.int32).t().contiguous()      # (n_look, B): each look-ahead step's column contiguous, made before the sync
     seq = torch.zeros((bsz, n_look, n_obj, 3), device=device)
 
-    def prepare(li, obj, shared=False):        # tool key-points, history frames and per-step tool motion of look-ahead step li
+    def prepare(li, obj, shared=False, order=None):        # tool key-points, history frames and per-step tool motion of look-ahead step li
         # (`shared`: every sample starts from the same cloud — its height is one reduction over n_obj values, not bsz of them: 28 -> 5 us at 256 x 1 000)
+        # (`order`: the ragged rollout's — row r of everything per sample is sample order[r]; `obj` is given in that order already)
         y = obj[0, :, 1].min().expand(bsz) if shared else obj[:, :, 1].min(dim=1).values
-        eef, dlt, raise_by = _place_tool_lean(task, decoded[:, li], action[:, li, 2], y, device, zero=obj_still[:, 0, 0])
+        dec, theta = decoded[:, li], action[:, li, 2]
+        if order is not None:
+            dec, theta = dec.index_select(0, order), theta.index_select(0, order)
+        eef, dlt, raise_by = _place_tool_lean(task, dec, theta, y, device, zero=obj_still[:, 0, 0])
         state0 = torch.cat([obj[:, None].expand(bsz, n_his, n_obj, 3), eef[:, None].expand(bsz, n_his, n_t, 3)], dim=2)
         delta = torch.cat([obj_still, dlt], dim=1)
         return state0, delta, raise_by
 
+    if ragged:
+        src = ppm_optimizer.physics_param if physics_param is None else physics_param
+        return _dynamics_ragged(model, device, task, state, phys, src[ppm_optimizer.material].dim() != 2, thr, rep_cols, seq, decoded, prepare,
+                                (attrs, p_instance, mask, tool_mask), n_t)
     # everything the first look-ahead step needs is enqueued BEFORE the call's one host sync, so that after it only the rollout's own launches
     # stand between the host and a busy GPU
     ready = prepare(0, state[None].expand(bsz, n_obj, 3), shared=True)
@@ -267,6 +325,42 @@ def dynamics(state, action, model, device, ppm_optimizer, physics_param=None):
         res = rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr, rep_cols[li],
                       max_steps[li], task["topk"], task["connect_tools_all"], n_t,
                       _lib.AG_HEIGHT_MIN, None, raise_by, out=direct)
+        if direct is None:
+            seq[:, li] = res
+    _strict_status(model, device)
+    return {"state_seqs": seq, "action_seqs": decoded}
+
+
+def _dynamics_ragged(model, device, task, state, phys, same_phys, thr, rep_cols, seq, decoded, prepare, const, n_t):
+    """dynamics() with model.ragged_rollout: every look-ahead push as ONE ag_rollout_ragged call that computes a sample for exactly its own
+    number of steps.  Per column the samples are ordered on the device (ag_rollout_order) and everything that differs between samples — the
+    action rows, a per-sample physics table (`same_phys`: one row for all) and, behind the first push, the previous frame — is gathered into
+    that order; attrs, p_instance and the masks are the same for every sample.  The library scatters each result back to its sample's row.
+    Still ONE host read: the per-step counts replace the step maximum of the plain form in it."""
+    attrs, p_instance, mask, tool_mask = const
+    n_look, bsz = rep_cols.shape
+    n_obj = state.shape[0]
+    orders, act_host = _ragged_plan(rep_cols, device)
+    first = state[None].expand(bsz, n_obj, 3)
+    ready = prepare(0, first, shared=True, order=orders[0])
+    copied = torch.cuda.Event()
+    copied.record(torch.cuda.current_stream(torch.device(device)))
+    model.take_status(device)
+    copied.synchronize()
+    for li in range(n_look):
+        n_steps = _ragged_steps(act_host[li])
+        order = orders[li] if n_steps is not None else None
+        rep = rep_cols[li]
+        if order is None:      # a push longer than the ragged call takes: the plain call on the batch as it is (one more host read for its step count)
+            n_steps = int(rep.max())
+            ready = prepare(li, first if li == 0 else seq[:, li - 1], shared=li == 0)
+        elif li > 0:
+            ready = prepare(li, seq[:, li - 1].index_select(0, order), order=order)
+        state0, delta, raise_by = ready
+        direct = seq[:, 0] if n_look == 1 else None
+        res = rollout(model, state0, delta, attrs, p_instance, phys if order is None or same_phys else phys.index_select(0, order), mask, tool_mask,
+                      thr, rep if order is None else rep.index_select(0, order), n_steps, task["topk"], task["connect_tools_all"], n_t,
+                      _lib.AG_HEIGHT_MIN, None, raise_by, out=direct, order=order, active=None if order is None else act_host[li])
         if direct is None:
             seq[:, li] = res
     _strict_status(model, device)
@@ -373,9 +467,23 @@ def dynamics_masked(state_init, state_mask, action, model, device, ppm_optimizer
     tool_mask[:, n_obj:] = True
     phys = _physics(ppm_optimizer, physics_param, bsz, device)
     thr = threshold_sq(ppm_optimizer.adj_thresh, bsz, torch.device(device), _lib.AG_VARIANT_BATCH)
-    n_steps = int(repeat.max().item())
-    model.take_status(device)
+    obj_mask, order, active = state_mask.bool(), None, None
+    n_steps = None
+    if getattr(model, "ragged_rollout", False):      # the per-step counts instead of the step maximum, in the same one host read
+        orders, act_host = _ragged_plan(repeat.to(torch.int32)[None].contiguous(), device)
+        copied = torch.cuda.Event()
+        copied.record(torch.cuda.current_stream(torch.device(device)))
+        model.take_status(device)
+        copied.synchronize()
+        n_steps = _ragged_steps(act_host[0])
+        if n_steps is not None:      # every per-sample input in the order of the call; the library scatters the result back
+            order, active = orders[0], act_host[0]
+            state0, delta, attrs, p_instance, mask, tool_mask, phys, repeat, obj_mask = (
+                t.index_select(0, order) for t in (state0, delta, attrs, p_instance, mask, tool_mask, phys, repeat, obj_mask))
+    if n_steps is None:
+        n_steps = int(repeat.max().item())
+        model.take_status(device)
     seq = rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr, repeat, n_steps, task["topk"],
-                  task["connect_tools_all"], n_t, _lib.AG_HEIGHT_MASKED_MEAN, state_mask.bool(), raise_by)
+                  task["connect_tools_all"], n_t, _lib.AG_HEIGHT_MASKED_MEAN, obj_mask, raise_by, order=order, active=active)
     _strict_status(model, device)
     return {"state_seqs": seq, "action_seqs": decoded}

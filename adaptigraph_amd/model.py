@@ -47,6 +47,10 @@ class _Dec(nn.Module):             # ParticlePredictor's `linear_{0,1,2}` (model
 
 
 class DynamicsPredictor(nn.Module):
+    # dynamics() / dynamics_masked(): roll every sample out for exactly its own number of steps (ag_rollout_ragged) instead of the batch's
+    # maximum; the same results bit for bit.  A plain attribute of the Python drivers, not an engine option; off unless the caller sets it
+    ragged_rollout = False
+
     def __init__(self, model_config, material_config, dataset_config, device):
         super().__init__()
         self.model_config = model_config
@@ -136,6 +140,9 @@ class DynamicsPredictor(nn.Module):
             warnings.warn("adaptigraph_amd: a forward produced non-finite values. If the inputs were finite, an activation of the fp16 "
                           "edge stack of precision mode 2 ('fast') left fp16's range (|x| > 65504): use "
                           "model.set_option('precision', 1).", RuntimeWarning, stacklevel=2)
+        if flags.value & _lib.AG_STATUS_ORDER:
+            warnings.warn("adaptigraph_amd: a ragged rollout was given a batch that is not sorted by non-increasing repeat, or an output row "
+                          "outside the batch; its results are undefined (include/adaptigraph_hip.h: ag_rollout_ragged).", RuntimeWarning, stacklevel=2)
         return flags.value
 
     def set_option(self, name, value, device=None):

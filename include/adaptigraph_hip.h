@@ -123,7 +123,9 @@ int ag_get_option(const ag_model *m, const char *name, int *value);
  * sum; with finite inputs both mean a checkpoint with large activations: switch the model to precision 1 (fp32 range).  In every mode,
  * non-finite inputs raise it through the message sums.  The reference has no counterpart (fp32 throughout, model.py:283-295).
  * (Until r03 bit 1 flagged mode-2 forwards that predicted motions above 0.125, where that round's arithmetic could leave the 1e-4 gate; the
- * r04 arithmetic has no such range and the bit is never set.) */
+ * r04 arithmetic has no such range and the bit is never set.)
+ * Bit 2 (AG_STATUS_ORDER, declared with ag_rollout_ragged): a ragged rollout was given a batch that is not in the promised order, or an output row
+ * outside the batch. */
 enum { AG_STATUS_NONFINITE = 1 };
 int ag_model_status(ag_model *m, int *flags /*host*/, ag_stream_t stream);
 
@@ -246,6 +248,43 @@ int ag_rollout_scripted(ag_model *m, const ag_scripted_params *p,
                         float *err,               /* (B, T); given exactly when gt is */
                         float *state_final,       /* (B, n_his, N, 3) or NULL: the history the last step's forward read */
                         void *workspace, size_t workspace_bytes, ag_stream_t stream);
+
+/* ---- ragged rollout: a sample is computed for exactly repeat[b] model steps.  ag_rollout runs every sample for n_steps = max(repeat) steps although
+ * a sample's prediction is recorded at step repeat[b] only (forward_dynamics.py:160-161) and nothing reads its later state: with push lengths sampled
+ * uniformly between the task limits (rope [5, 15), granular and cloth [2, 10)) a third or more of the sample-steps are discarded.  Graphs of a batch
+ * never interact, so leaving them out changes no recorded bit.  One mechanism, for the plain and the shared-state driver: the batch is ORDERED by
+ * non-increasing repeat, the samples still running at step s are then a prefix of the batch, and the host — which knows the prefix length of every
+ * step — sizes every launch of step s for it.
+ *
+ * ag_rollout_order: the ordering contract, computed on the device in ONE launch (no scratch, no host synchronisation, no allocation; capturable):
+ *   order[r]  (B) = the sample of rank r: sorted by repeat DESCENDING (negative values count as 0), ties by ASCENDING index — a stable sort,
+ *             deterministic: two calls give the same words
+ *   active[s] (AG_RAGGED_MAX_STEPS + 1) = #{b : repeat[b] >= s + 1} for s < AG_RAGGED_MAX_STEPS: the samples that run model step s + 1; the LAST word
+ *             counts the samples with repeat > AG_RAGGED_MAX_STEPS (non-zero: the batch is not for ag_rollout_ragged)
+ * Any B >= 1.  The number of model steps of the batch is the number of non-zero words among the first AG_RAGGED_MAX_STEPS.
+ *
+ * ag_rollout_ragged: ag_rollout on inputs the caller has gathered into that order (input row r = sample order[r] of the original batch; repeat too), and
+ *   active_per_step (HOST, p->n_steps words, read when the call is enqueued) = active[0 .. n_steps): model step s (1-based) runs the edge builder, the
+ *             forward and the state step for the samples [0, active_per_step[s - 1]) only.  Table bases and row numbers stay those of the whole batch;
+ *             counts and grids shrink, so a running sample's rows are computed exactly as ag_rollout computes them: out_seq holds ag_rollout's bits
+ *   out_index (device, B; may be NULL = the identity): sample b's row of out_seq and of state_final is out_index[b] — pass `order` and the results land in
+ *             the original batch's rows.  Rows of samples with repeat outside 1..n_steps are left untouched, as by ag_rollout
+ *   state_final[out_index[b]] = sample b's history right AFTER ITS OWN step repeat[b] (state0[b] for repeat[b] <= 0) — not the history after n_steps
+ *             steps, which ag_rollout returns and this call never computes
+ * One stream: "rollout_streams" and "cu_split" are ignored; "shared_state" applies as in ag_rollout (the base is input sample 0 without its tools and runs
+ * every step); every other option as in ag_rollout.  Workspace: ag_rollout_workspace_bytes_for(m, p), the same carving.  No host synchronisation.
+ * AG_ERR_ARG, before anything is launched: a null argument, n_steps > AG_RAGGED_MAX_STEPS, active_per_step not non-increasing, above B or below 0.
+ * On the device: if repeat is not in non-increasing order, or an out_index[b] is outside [0, B), the model's sticky status gets AG_STATUS_ORDER
+ * (ag_model_status) and a write to such a row is skipped; every index the call forms is bounded by B whatever repeat holds, so misuse gives undefined
+ * VALUES, never an access out of bounds. */
+enum { AG_RAGGED_MAX_STEPS = 1024 };
+enum { AG_STATUS_ORDER = 4 };
+int ag_rollout_order(const int32_t *repeat, int B, int32_t *order /*B*/, int32_t *active /*AG_RAGGED_MAX_STEPS + 1*/, ag_stream_t stream);
+int ag_rollout_ragged(ag_model *m, const ag_rollout_params *p, const float *state0, const float *delta, const float *attrs,
+                      const float *p_instance, const float *phys, const uint8_t *mask, const uint8_t *tool_mask,
+                      const uint8_t *obj_mask, const float *thr_sq, const int32_t *repeat,
+                      const int32_t *active_per_step /*host, p->n_steps*/, const int32_t *out_index /*device, B, may be NULL*/,
+                      float *out_seq, float *state_final, void *workspace, size_t workspace_bytes, ag_stream_t stream);
 
 /* chamfer(x, y) of src/planning/losses.py:4-10 — the MPPI error term:
  *   x (B,N,3) predicted particles, y (B,M,3) if y_batched else (1,M,3) target cloud  ->  out (B)
