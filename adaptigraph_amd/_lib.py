@@ -25,6 +25,7 @@ AG_STATUS_NONFINITE, AG_STATUS_ORDER = 1, 4
 AG_PENALTIES = {None: 0, "rope": 1, "cloth": 2, "granular": 3}      # AG_PENALTY_*
 AG_ERROR_GIVEN, AG_ERROR_BOX = 0, 1
 AG_PLAN_TERMS = 9
+AG_EMD_MAX_POINTS = 1024
 
 c_void_p, c_char_p, c_int, c_int32, c_int64, c_size_t, c_float, c_double, P = (
     ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float, ctypes.c_double,
@@ -112,6 +113,10 @@ SIGNATURES = {
     "ag_chamfer_tiled_workspace_bytes": (c_size_t, [c_int] * 3),
     "ag_chamfer_tiled": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "ag_chamfer_tiled_backward": (c_int, [c_void_p] * 7 + [c_int] * 4 + [c_void_p] * 3),
+    # matching losses: earth-mover assignment, its backward, directed Hausdorff maxima
+    "ag_emd": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 4),
+    "ag_emd_backward": (c_int, [c_void_p] * 5 + [c_int] * 4 + [c_void_p] * 3),
+    "ag_hausdorff": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3),
     # the planner's trajectory cost
     "ag_plan_cost_workspace_bytes": (c_size_t, [P(PlanCostParams)]),
     "ag_plan_cost": (c_int, [P(PlanCostParams)] + [c_void_p] * 7 + [c_size_t, c_void_p]),

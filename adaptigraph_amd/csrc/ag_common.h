@@ -608,6 +608,15 @@ int ag_launch_chamfer_tiled(const float *x, const float *y, const unsigned char 
 int ag_launch_chamfer_tiled_backward(const float *x, const unsigned char *xmask, const float *y, const unsigned char *ymask, const int *idx_x,
                                      const int *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy,
                                      hipStream_t s);
+// the matching losses (ag_match.hip): exact assignment of two clouds by one wave per sample (kEmdMaxPoints = AG_EMD_MAX_POINTS a side), its
+// gather-form backward, and the directed Hausdorff maxima with both clouds in LDS (ag_chamfer's size limit).  -1: a size is out of range.
+constexpr int kEmdMaxPoints = 1024;
+int ag_launch_emd(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M, int y_batched,
+                  float *out, int *col, int *row, hipStream_t s);
+int ag_launch_emd_backward(const float *x, const float *y, const int *col, const int *row, const float *grad_out, int B, int N, int M, int y_batched,
+                           float *gx, float *gy, hipStream_t s);
+int ag_launch_hausdorff(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M, int y_batched,
+                        float *out, int *arg, hipStream_t s);
 // the planner's trajectory cost (ag_plan_cost.hip): one wave per (b, l) cloud, then one workgroup for the normalisers and the rewards.
 // The thresholds are the reference's Python doubles rounded to float once, as a tensor op rounds its scalar operand.
 struct AgPlanCostArgs {

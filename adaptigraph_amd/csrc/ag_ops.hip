@@ -109,6 +109,51 @@ int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float
     return AG_OK;
 }
 
+// ---- the matching losses (ag_match.hip) ----
+static_assert(kEmdMaxPoints == AG_EMD_MAX_POINTS, "the kernel's register budget and the header's limit are one number");
+
+int ag_emd(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched, float *out,
+           int32_t *col, int32_t *row, ag_stream_t stream)
+{
+    const char *who = "ag_emd";
+    if (!x || !y || !out || !col || !row) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
+    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (N > AG_EMD_MAX_POINTS || M > AG_EMD_MAX_POINTS)
+        return ag_fail(AG_ERR_ARG, "%s: N=%d M=%d exceed AG_EMD_MAX_POINTS = %d points a side", who, N, M, AG_EMD_MAX_POINTS);
+    if (ag_launch_emd(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, col, row, static_cast<hipStream_t>(stream)) != 0)
+        return ag_fail(AG_ERR_ARG, "%s: bad sizes N=%d M=%d", who, N, M);
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_emd_backward(const float *x, const float *y, const int32_t *col, const int32_t *row, const float *grad_out, int B, int N, int M, int y_batched,
+                    float *gx, float *gy, ag_stream_t stream)
+{
+    const char *who = "ag_emd_backward";
+    if (!x || !y || !col || !row || !grad_out || !gx) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
+    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (N > AG_EMD_MAX_POINTS || M > AG_EMD_MAX_POINTS)
+        return ag_fail(AG_ERR_ARG, "%s: N=%d M=%d exceed AG_EMD_MAX_POINTS = %d points a side", who, N, M, AG_EMD_MAX_POINTS);
+    ag_launch_emd_backward(x, y, col, row, grad_out, B, N, M, y_batched ? 1 : 0, gx, gy, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_hausdorff(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched, float *out,
+                 int32_t *arg, ag_stream_t stream)
+{
+    const char *who = "ag_hausdorff";
+    if (!x || !y || !out || !arg) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
+    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if ((long long)N + M > 12800) return ag_fail(AG_ERR_ARG, "%s: N + M = %lld exceeds the LDS-resident limit (12800 points)", who, (long long)N + M);
+    if (ag_launch_hausdorff(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, arg, static_cast<hipStream_t>(stream)) != 0)
+        return ag_fail(AG_ERR_HIP, "%s: the kernel's LDS size was refused", who);
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 // ---- the planner's trajectory cost (ag_plan_cost.hip) ----
 static const char *plan_cost_refusal(const ag_plan_cost_params *p)
 {

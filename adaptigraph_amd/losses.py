@@ -155,3 +155,87 @@ def granular_penalty(state_pred, action, state_init, sim_real_ratio=10.0):
     s2d = _states_before_push(state_pred, state_init)                                                         # (bsz, L, n, 2)
     d = (pts[:, :, :, None] - s2d[:, :, None]).norm(dim=-1).min(dim=-1).values.min(dim=-1).values
     return torch.exp(-(d - 0.02 * sim_real_ratio).clamp_min(0) * 100.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# Losses without particle correspondence (src/dynamics/gnn/loss.py): earth-mover and Hausdorff distance
+# ---------------------------------------------------------------------------------------------------------------------
+def _clouds_and_masks(x, y, x_mask, y_mask, who):
+    """The contiguous fp32 clouds and u8 masks a matching kernel reads, and y_batched; shapes checked before anything is launched."""
+    _require_gpu(x, "x")
+    _require_gpu(y, "y")
+    if x.dim() != 3 or y.dim() != 3 or x.shape[2] != 3 or y.shape[2] != 3:
+        raise ValueError(f"{who}: x (B,N,3) and y (B or 1,M,3) expected, got {tuple(x.shape)} and {tuple(y.shape)}")
+    if y.shape[0] not in (1, x.shape[0]):
+        raise ValueError(f"{who}: y holds {y.shape[0]} clouds for {x.shape[0]} samples (1 or {x.shape[0]} expected)")
+    if (x_mask is None) != (y_mask is None):
+        raise ValueError(f"{who}: give both masks or neither")
+    x = x.contiguous().float()
+    y = y.to(x.device).contiguous().float()
+    xm = ym = None
+    if x_mask is not None:
+        xm, ym = _lib._u8(x_mask.ne(0), x.device), _lib._u8(y_mask.ne(0), x.device)
+        if xm.shape != x.shape[:2] or ym.shape != y.shape[:2]:
+            raise ValueError(f"{who}: masks {tuple(xm.shape)} / {tuple(ym.shape)} do not match the clouds")
+    return x, y, xm, ym, _y_batched(x, y)
+
+
+def _emd_forward(x, y, xm, ym, y_batched):
+    B, N, M = x.shape[0], x.shape[1], y.shape[1]
+    out = torch.empty(B, dtype=torch.float32, device=x.device)
+    col = torch.empty((B, N), dtype=torch.int32, device=x.device)
+    row = torch.empty((B, M), dtype=torch.int32, device=x.device)
+    _lib.call("ag_emd", x.device, x, xm, y, ym, B, N, M, y_batched, out, col, row)
+    return out, col, row
+
+
+class _Emd(torch.autograd.Function):
+    """`ag_emd` with `ag_emd_backward`: the assignment is piecewise constant in the coordinates, so the gradient is that of the matched pairs'
+    distances (what autograd gives the reference through its gather, loss.py:46-54).  Same value bits as the call without grad."""
+
+    @staticmethod
+    def forward(ctx, x, y, xm, ym, y_batched):
+        out, col, row = _emd_forward(x, y, xm, ym, y_batched)
+        ctx.save_for_backward(x, y, col, row)
+        ctx.y_batched = y_batched
+        ctx.mark_non_differentiable(col, row)
+        return out, col, row
+
+    @staticmethod
+    def backward(ctx, grad_out, _gcol, _grow):
+        x, y, col, row = ctx.saved_tensors
+        B, N, M = x.shape[0], x.shape[1], y.shape[1]
+        want_y = ctx.needs_input_grad[1]
+        g = grad_out.contiguous().float()
+        gx = torch.empty_like(x)
+        gy = torch.empty((B, M, 3), dtype=torch.float32, device=x.device) if want_y else None      # (a broadcast y: per-sample rows, summed into row 0)
+        _lib.call("ag_emd_backward", x.device, x, y, col, row, g, B, N, M, ctx.y_batched, gx, gy)
+        if want_y and y.shape[0] != B:
+            gy = gy[:1]
+        return gx, gy, None, None, None
+
+
+def emd(x, y, x_mask=None, y_mask=None, return_assignment=False):
+    """x (B,N,3), y (B or 1,M,3) -> (B,): the mean distance of the pairs of the minimum-cost assignment of the smaller (valid) cloud into the
+    larger, EarthMoverLoss.em_distance of dynamics/gnn/loss.py:29-55 per sample, on the device in one launch (`ag_emd`: exact, N, M <=
+    AG_EMD_MAX_POINTS).  x_mask (B,N) / y_mask (B or 1,M): points that take part, both or neither.  A sample with an empty side or a non-finite
+    valid coordinate is NaN.  Differentiable in x and y; the value bits are the same with and without grad.
+    return_assignment: also col (B,N) and row (B,M) int32, the partner of every point or -1."""
+    x, y, xm, ym, y_batched = _clouds_and_masks(x, y, x_mask, y_mask, "emd")
+    if _needs_grad(x, y):
+        out, col, row = _Emd.apply(x, y, xm, ym, y_batched)
+    else:
+        out, col, row = _emd_forward(x, y, xm, ym, y_batched)
+    return (out, col, row) if return_assignment else out
+
+
+def hausdorff(x, y, x_mask=None, y_mask=None):
+    """x (B,N,3), y (B or 1,M,3) -> (values (B,2), arg (B,4) int32): per sample [max_n min_m ||x_n - y_m||, max_m min_n ||x_n - y_m||] over the
+    valid points and the indices (n*, its nearest m, m*, its nearest n), ties to the lowest index; NaN / -1 for a sample with an empty side
+    (`ag_hausdorff`, N + M <= 12 800).  The values carry no gradient: `gnn_loss.HausdorffLoss` re-evaluates the selected pairs with tensor ops."""
+    x, y, xm, ym, y_batched = _clouds_and_masks(x, y, x_mask, y_mask, "hausdorff")
+    B, N, M = x.shape[0], x.shape[1], y.shape[1]
+    out = torch.empty((B, 2), dtype=torch.float32, device=x.device)
+    arg = torch.empty((B, 4), dtype=torch.int32, device=x.device)
+    _lib.call("ag_hausdorff", x.device, x.detach(), xm, y.detach(), ym, B, N, M, y_batched, out, arg)
+    return out, arg

@@ -16,6 +16,7 @@ from torch.utils.data import DataLoader
 from . import train_ops
 
 from .dataset import DeviceBatcher, DynDataset, attach_edges
+from .gnn_loss import build_loss_funcs, parse_loss_spec
 from .train_model import TrainableDynamicsPredictor, unrolled_loss
 
 
@@ -48,10 +49,13 @@ class _Indices(torch.utils.data.Dataset):
 def train(config):
     """-> {'train': [mean logged loss per epoch], 'valid': [...]}.
     train_config['device_batches'] (default false): the batches are assembled on the GPU from positions resident in HBM (`DeviceBatcher`): same
-    DataLoader sample order and same values as the host loader with num_workers=0 under the same seed."""
+    DataLoader sample order and same values as the host loader with num_workers=0 under the same seed.
+    train_config['loss_funcs'] (optional): [[name, weight], ...] with names among mse, chamfer, emd, hausdorff (`gnn_loss`), the list of
+    train.py:61-62; the non-MSE losses take the batch's `obj_mask` as the mask of both clouds.  Absent: the MSE objective."""
     dataset_config, train_config = config["dataset_config"], config["train_config"]
     model_config, material_config = config["model_config"], config["material_config"]
     data_name = dataset_config["data_name"]
+    loss_spec = parse_loss_spec(train_config["loss_funcs"]) if "loss_funcs" in train_config else None      # (ValueError before any GPU work)
     ckpt_dir = os.path.join(train_config["out_dir"], data_name, "checkpoints")
     os.makedirs(ckpt_dir, exist_ok=True)
     set_seed(train_config["random_seed"])
@@ -87,7 +91,10 @@ def train(config):
                     # parameter gradients straight into .grad for this forward + backward only (train_ops.DIRECT_GRADS is a
                     # process-wide switch: code that asks autograd for parameter gradients must find it off)
                     with train_ops.direct_grads(ph == "train" and getattr(model, "fused_dense", False)):
-                        loss = unrolled_loss(model, data, n_future)
+                        if loss_spec is None:
+                            loss = unrolled_loss(model, data, n_future)
+                        else:
+                            loss = unrolled_loss(model, data, n_future, build_loss_funcs(loss_spec, data["obj_mask"]))
                         if ph == "train":
                             loss.backward()
                     if ph == "train":

@@ -338,6 +338,39 @@ int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float
                               const int32_t *idx_y, const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy,
                               ag_stream_t stream);
 
+/* ---- the training losses of src/dynamics/gnn/loss.py that need no particle correspondence between prediction and label ---- */
+
+/* Points a side of ag_emd (one wave per sample keeps the column side in registers): the largest size whose worst case stays well under a second
+ * per launch on a shared device. */
+#define AG_EMD_MAX_POINTS 1024
+
+/* EarthMoverLoss.em_distance of src/dynamics/gnn/loss.py:29-55 without its host round trip (the (B,N,M) distance tensor of :32-34, the copy and
+ * scipy.optimize.linear_sum_assignment per sample of :39-42, the gather of :46-51): the exact minimum-cost assignment of two clouds, one launch.
+ *   x (B,N,3), y (B,M,3) if y_batched else (1,M,3); x_mask (B,N) / y_mask (B|1,M) u8, both given or both NULL; 1 <= N, M <= AG_EMD_MAX_POINTS.
+ *   cost of a pair: c[n,m] = sqrtf((dx dx + dy dy) + dz dz) in fp32, products rounded separately, widened to fp64.
+ *   With Nx / My the valid counts and K = min(Nx, My): an injection of the smaller valid set into the larger that minimises the fp64 sum of c
+ *   (shortest augmenting paths with fp64 duals: exact, and where several assignments are optimal always the same one).
+ *   col (B,N) int32: the partner of x[b,n] in y, -1 for a masked or unmatched point; row (B,M) int32: the inverse.
+ *   out (B): float(S / K), S the fp64 sum of the matched c in ascending n (loss.py:54 per sample when N == M and nothing is masked).
+ * K == 0, or a NaN / +-Inf among a sample's valid coordinates: out = NaN and every index -1 for that sample alone.
+ * No atomics, no scratch, no host read, no memset: bit-reproducible and capturable in a HIP graph. */
+int ag_emd(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched, float *out,
+           int32_t *col, int32_t *row, ag_stream_t stream);
+
+/* Backward of ag_emd for grad_out (B) = dL/dout with the assignment that call wrote (autograd through the gather and norm of loss.py:46-54):
+ *   gx[b,n] = g_b u(x_n - y_col[n]) / K if col[n] >= 0 else 0;  gy[b,m] = g_b u(y_m - x_row[m]) / K if row[m] >= 0 else 0;  u(v) = v / ||v||, u(0) = 0,
+ * K the number of matched pairs.  gx (B,N,3); gy may be NULL; for a broadcast y it is a (B,M,3) buffer as in ag_chamfer_backward: row 0 holds the
+ * per-sample rows summed in ascending b on return.  Gather form, no atomics. */
+int ag_emd_backward(const float *x, const float *y, const int32_t *col, const int32_t *row, const float *grad_out, int B, int N, int M, int y_batched,
+                    float *gx, float *gy, ag_stream_t stream);
+
+/* The per-sample directed maxima of HausdorffLoss.hausdorff_distance, src/dynamics/gnn/loss.py:70-75 (which then takes the maxima over the batch):
+ * clouds and masks as ag_emd, sizes as ag_chamfer (N + M <= 12800).
+ *   out (B,2) = [max_n min_m c, max_m min_n c] over the valid points, c as in ag_emd: max, min and sqrtf are exact, so these are the formula's bits.
+ *   arg (B,4) int32 = n*, its nearest m, m*, its nearest n; ties go to the lowest index.  An empty side: NaN and -1. */
+int ag_hausdorff(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched, float *out,
+                 int32_t *arg, ag_stream_t stream);
+
 /* ---- the planner's trajectory cost ("MPPI glue on device"): everything of running_cost, src/planning/plan.py:27-59, but the
  * error term's own kernel — the penalties rope_penalty / cloth_penalty / granular_penalty and box_loss of src/planning/losses.py:26-92, the
  * workspace-bounds term of plan.py:41-51 and the reward of plan.py:37 and 53 — in two launches that read every predicted cloud once.
