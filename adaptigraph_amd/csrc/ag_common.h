@@ -593,6 +593,12 @@ void ag_launch_gather_clouds(const float *store, const int64_t *episodes, int n_
                              float *pts, int32_t *count, hipStream_t s);
 void ag_launch_assemble_batch(const ag_batch_dims &d, const float *obj, const void *tool, const int64_t *episodes, const int32_t *epi,
                               const int32_t *frames, const int32_t *picks, const double *noise, const float *rot, const ag_batch_out &o, hipStream_t s);
+// the cloud-distance operators (ag_cost.hip, ag_cost_tiled.hip, ag_match.hip; shared device code: ag_cloud_dev.h).
+// The resident kernels (chamfer, Hausdorff) keep both clouds of a sample in the LDS of one workgroup as fp32 planes: 12 800 points are 150 KB.
+constexpr int kCloudResidentPoints = 12800;
+inline bool ag_cloud_resident(int N, int M) { return (long long)N + M <= kCloudResidentPoints; }
+// a backward's gy holds one (len) row per sample; for a broadcast target (gy wanted, y_batched = 0, B > 1) row 0 receives their sum in ascending b
+void ag_launch_sum_rows(float *gy, int B, int len, int y_batched, hipStream_t s);
 int ag_launch_chamfer(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,
                       int y_batched, float *out, hipStream_t s);
 int ag_launch_chamfer_idx(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M,

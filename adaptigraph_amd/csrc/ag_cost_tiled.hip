@@ -4,7 +4,8 @@
 // sample is split into query tiles of kChamTQ points (one workgroup each, four query points per thread in registers, as there) and the OTHER
 // cloud streams through LDS in chunks of kChamTO points in ascending index order; the minimum is carried across chunks in registers.
 // Bit equality with the resident kernels, wherever both apply:
-//   - per pair the arithmetic is the same expression under the same flags ((d0 d0 + d1 d1) + d2 d2, products rounded separately);
+//   - the per-pair arithmetic, the reduction tail and the backward's pieces are the same code (ag_cloud_dev.h), the sweep's inner loop the
+//     same text as chamfer_sweep's in ag_cost.hip (why it is not one function: see there);
 //   - min is exact in any order, and with indices a strict < over ascending indices sends ties to the lowest index in both forms;
 //   - the sweep only WRITES sqrt(min) per query point (near[B][M + N]); a second kernel, one workgroup per sample, adds them in the order
 //     the resident kernel adds them: thread tid takes points tid, tid + 256, ... (the resident tid + 1024 j + 256 k, k = 0..3 inside j, is
@@ -12,13 +13,11 @@
 // The backward is the gather form of chamfer_bwd_kernel with the other side's index row streamed in chunks: per query point the matches are
 // added in ascending index order, then the point's own nearest term, then the same scaling.  No atomics anywhere, nothing to zero, no host
 // synchronisation: every launch goes to the caller's stream.
-#include "ag_common.h"
+#include "ag_cloud_dev.h"
 
 namespace {
 
-typedef float ag_f2 __attribute__((ext_vector_type(2)));
-constexpr int kQ = 4;                       // query points per thread
-constexpr int kTQ = kChamTQ, kTO = kChamTO;
+constexpr int kQ = kChamQ, kTQ = kChamTQ, kTO = kChamTO;
 static_assert(kTQ == 256 * kQ, "a query tile is four points per thread of a 256-thread workgroup");
 static_assert(kTO % 4 == 0, "chunks hold whole point pairs (forward) and whole int4 index groups (backward)");
 constexpr float kInvalid = -1.f;            // near[] marker of an invalid query point (sqrt never returns a negative value)
@@ -74,8 +73,7 @@ __global__ __launch_bounds__(256) void chamfer_tiled_sweep_kernel(const float *x
                         Z = *reinterpret_cast<const ag_f2 *>(so + 2 * kTO + n);
 #pragma unroll
             for (int k = 0; k < kQ; ++k) {
-                const ag_f2 d0 = X - a0[k], d1 = Y - a1[k], d2 = Z - a2[k];
-                const ag_f2 d = (d0 * d0 + d1 * d1) + d2 * d2;
+                const ag_f2 d = pair_d2<ag_f2>(X - a0[k], Y - a1[k], Z - a2[k]);
                 if constexpr (IDX) {
                     if (d.x < best[k]) { best[k] = d.x; bi[k] = c0 + n; }
                     if (d.y < best[k]) { best[k] = d.y; bi[k] = c0 + n + 1; }
@@ -111,29 +109,13 @@ __global__ __launch_bounds__(256) void chamfer_tiled_finish_kernel(const float *
         const float v = nx_[q];
         if (v != kInvalid) { s_x += v; c_x += 1.f; }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        s_y += __shfl_xor(s_y, o); s_x += __shfl_xor(s_x, o);
-        c_y += __shfl_xor(c_y, o); c_x += __shfl_xor(c_x, o);
-    }
-    if (lane == 0) { red[0][wave] = s_y; red[1][wave] = s_x; red[2][wave] = c_y; red[3][wave] = c_x; }
+    float acc[4] = {s_y, s_x, c_y, c_x};
+    four_wave_park(acc, red, lane, wave);
     __syncthreads();
-    if (tid == 0) {
-        const float ny = (red[2][0] + red[2][1]) + (red[2][2] + red[2][3]), nx = (red[3][0] + red[3][1]) + (red[3][2] + red[3][3]);
-        const float v = ((red[0][0] + red[0][1]) + (red[0][2] + red[0][3])) / ny + ((red[1][0] + red[1][1]) + (red[1][2] + red[1][3])) / nx;
-        out[b] = (nx > 0.f && ny > 0.f) ? v : NAN;
-    }
+    if (tid == 0) out[b] = chamfer_value(red);
 }
 
-// ---- backward (the formulas of ag_cost.hip: chamfer_bwd_kernel) ----
-
-__device__ __forceinline__ void unit_add(float ax, float ay, float az, const float *o, float &sx, float &sy, float &sz)
-{
-    const float d0 = ax - o[0], d1 = ay - o[1], d2 = az - o[2];
-    const float r = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-    if (r > 0.f) { sx += d0 / r; sy += d1 / r; sz += d2 / r; }
-}
-
+// ---- backward (the gather form of ag_cloud_dev.h, the other side's index row streamed through LDS in chunks) ----
 // side 0 = gx (the particles as queries, the target's index row idx_y streamed), side 1 = gy; tiles_y = 0 when gy is not wanted
 __global__ __launch_bounds__(256) void chamfer_tiled_bwd_kernel(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask,
                                                                 const int *idx_x, const int *idx_y, const float *grad_out, int N, int M,
@@ -143,81 +125,38 @@ __global__ __launch_bounds__(256) void chamfer_tiled_bwd_kernel(const float *x, 
     __shared__ float red[2][4];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const TileId t = tile_of(blockIdx.x, (N + kTQ - 1) / kTQ, tiles_y);
-    const int b = t.b, by = y_batched ? b : 0;
-    const float *xb = x + (size_t)b * N * 3, *yb = y + (size_t)by * M * 3;
-    const unsigned char *xm = xmask ? xmask + (size_t)b * N : nullptr, *ym = ymask ? ymask + (size_t)by * M : nullptr;
+    const int b = t.b;
+    const CloudSample c = cloud_sample(x, y, xmask, ymask, N, M, y_batched, b);
     const int *ixb = idx_x + (size_t)b * N, *iyb = idx_y + (size_t)b * M;
-    // the valid counts, recounted from the masks: float adds of 1, exact (in any order) up to 2^24
-    float cx = 0.f, cy = 0.f;
+    float cnt[2] = {0.f, 0.f};      // the valid counts of x, of y, recounted from the masks
     for (int i = tid; i < N; i += 256)
-        if (!xm || xm[i]) cx += 1.f;
+        if (!c.xm || c.xm[i]) cnt[0] += 1.f;
     for (int i = tid; i < M; i += 256)
-        if (!ym || ym[i]) cy += 1.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { cx += __shfl_xor(cx, o); cy += __shfl_xor(cy, o); }
-    if (lane == 0) { red[0][wave] = cx; red[1][wave] = cy; }
-    __syncthreads();
-    const float nx = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]), my = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-    const bool both = nx > 0.f && my > 0.f;                  // an empty side: the value is NaN, the gradient zero
-    const float inv_x = both ? 1.f / nx : 0.f, inv_y = both ? 1.f / my : 0.f, g = grad_out[b];
+        if (!c.ym || c.ym[i]) cnt[1] += 1.f;
+    float inv_x, inv_y;
+    chamfer_inv_counts(cnt, red, lane, wave, inv_x, inv_y);
+    const float g = grad_out[b];
 
     const bool sx = t.side == 0;
-    const float *qp = sx ? xb : yb, *op = sx ? yb : xb;
-    const unsigned char *qm = sx ? xm : ym;
+    const float *qp = sx ? c.xb : c.yb, *op = sx ? c.yb : c.xb;
+    const unsigned char *qm = sx ? c.xm : c.ym;
     const int *idx_q = sx ? ixb : iyb, *io = sx ? iyb : ixb;
     const int Q = sx ? N : M, On = sx ? M : N;
     const float inv_q = sx ? inv_x : inv_y, inv_o = sx ? inv_y : inv_x;
     float *gq = sx ? gx + (size_t)b * N * 3 : gy + (size_t)b * M * 3;
 
-    int key[kQ];
-    float a0[kQ], a1[kQ], a2[kQ], s0[kQ], s1[kQ], s2[kQ];
-#pragma unroll
-    for (int k = 0; k < kQ; ++k) {
-        const int q = t.tile * kTQ + tid + 256 * k;
-        const bool ok = q < Q && (!qm || qm[q]);
-        key[k] = ok ? q : -2;                                // -2 matches no index entry (entries are >= -1)
-        a0[k] = ok ? qp[3 * (size_t)q] : 0.f; a1[k] = ok ? qp[3 * (size_t)q + 1] : 0.f; a2[k] = ok ? qp[3 * (size_t)q + 2] : 0.f;
-        s0[k] = s1[k] = s2[k] = 0.f;
-    }
+    const int q0 = t.tile * kTQ + tid;
+    ChamferBwdQuery r;
+    chamfer_bwd_load(r, q0, qp, qm, Q);
     for (int c0 = 0; c0 < On; c0 += kTO) {
         const int len = min(kTO, On - c0), len4 = (len + 3) & ~3;      // (padded with -1 to a multiple of 4)
         if (c0) __syncthreads();
         for (int i = tid; i < len4; i += 256) si[i] = i < len ? io[c0 + i] : -1;
         __syncthreads();
-        for (int j = 0; j < len4; j += 4) {
-            const int4 e = *reinterpret_cast<const int4 *>(si + j);
-            const float *oj = op + 3 * (size_t)(c0 + j);      // (read only behind a match, and a match is an entry below On)
-#pragma unroll
-            for (int k = 0; k < kQ; ++k) {
-                if (e.x == key[k]) unit_add(a0[k], a1[k], a2[k], oj + 0, s0[k], s1[k], s2[k]);
-                if (e.y == key[k]) unit_add(a0[k], a1[k], a2[k], oj + 3, s0[k], s1[k], s2[k]);
-                if (e.z == key[k]) unit_add(a0[k], a1[k], a2[k], oj + 6, s0[k], s1[k], s2[k]);
-                if (e.w == key[k]) unit_add(a0[k], a1[k], a2[k], oj + 9, s0[k], s1[k], s2[k]);
-            }
-        }
+        // (a point's coordinates are read only behind a match, and a match is an entry below On)
+        for (int j = 0; j < len4; j += 4) chamfer_bwd_scan4(r, *reinterpret_cast<const int4 *>(si + j), op + 3 * (size_t)(c0 + j));
     }
-#pragma unroll
-    for (int k = 0; k < kQ; ++k) {
-        const int q = t.tile * kTQ + tid + 256 * k;
-        if (q >= Q) continue;
-        float t0 = 0.f, t1 = 0.f, t2 = 0.f;
-        const int nn = key[k] >= 0 ? idx_q[q] : -1;
-        if (nn >= 0 && nn < On) unit_add(a0[k], a1[k], a2[k], op + 3 * (size_t)nn, t0, t1, t2);      // (nn < On: never read past a cloud for a bad index)
-        const bool live = key[k] >= 0 && inv_q > 0.f;
-        gq[3 * (size_t)q + 0] = live ? g * (t0 * inv_q + s0[k] * inv_o) : 0.f;
-        gq[3 * (size_t)q + 1] = live ? g * (t1 * inv_q + s1[k] * inv_o) : 0.f;
-        gq[3 * (size_t)q + 2] = live ? g * (t2 * inv_q + s2[k] * inv_o) : 0.f;
-    }
-}
-
-// gy[i] = sum_b gy[b * len + i] in ascending b, in place (row 0 receives the sum)
-__global__ __launch_bounds__(256) void chamfer_tiled_sum_rows_kernel(float *gy, int B, int len)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= len) return;
-    float s = gy[i];
-    for (int b = 1; b < B; ++b) s += gy[(size_t)b * len + i];
-    gy[i] = s;
+    chamfer_bwd_store(r, q0, Q, idx_q, op, On, g, inv_q, inv_o, gq);
 }
 
 }  // namespace
@@ -249,7 +188,6 @@ int ag_launch_chamfer_tiled_backward(const float *x, const unsigned char *xmask,
     if (blocks > 0x7fffffffLL) return -1;
     hipLaunchKernelGGL(chamfer_tiled_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, y, xmask, ymask, idx_x, idx_y, grad_out, N, M, y_batched,
                        tiles_y, gx, gy);
-    if (gy && !y_batched && B > 1)
-        hipLaunchKernelGGL(chamfer_tiled_sum_rows_kernel, dim3((3 * M + 255) / 256), dim3(256), 0, s, gy, B, 3 * M);
+    ag_launch_sum_rows(gy, B, 3 * M, y_batched, s);
     return 0;
 }

@@ -9,15 +9,9 @@
 //
 // cost of a pair: c = sqrtf((dx dx + dy dy) + dz dz) in fp32 with separately rounded products (-ffp-contract=off), widened to fp64
 // for the solver: duals, path lengths and the sum are fp64.
-#include "ag_common.h"
+#include "ag_cloud_dev.h"
 
 namespace {
-
-__device__ __forceinline__ float pair_cost(float ax, float ay, float az, float bx, float by, float bz)
-{
-    const float d0 = ax - bx, d1 = ay - by, d2 = az - bz;
-    return sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
-}
 
 __device__ __forceinline__ bool finite3(const float *p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]); }
 
@@ -217,7 +211,7 @@ __device__ __forceinline__ void emd_bwd_side(const float *q, const float *o, con
         float g0 = 0.f, g1 = 0.f, g2 = 0.f;
         if (p >= 0) {
             const float d0 = q[3 * i] - o[3 * p], d1 = q[3 * i + 1] - o[3 * p + 1], d2 = q[3 * i + 2] - o[3 * p + 2];
-            const float r = sqrtf((d0 * d0 + d1 * d1) + d2 * d2);
+            const float r = sqrtf(pair_d2(d0, d1, d2));
             if (r > 0.f) { g0 = g * ((d0 / r) * inv_k); g1 = g * ((d1 / r) * inv_k); g2 = g * ((d2 / r) * inv_k); }
         }
         gq[3 * i] = g0; gq[3 * i + 1] = g1; gq[3 * i + 2] = g2;
@@ -242,17 +236,6 @@ __global__ __launch_bounds__(256) void emd_bwd_kernel(const float *x, const floa
     const float inv_k = K > 0 ? 1.f / (float)K : 0.f, g = grad_out[b];
     emd_bwd_side(xb, yb, colb, N, g, inv_k, tid, gx + (size_t)b * N * 3);
     if (gy) emd_bwd_side(yb, xb, rowb, M, g, inv_k, tid, gy + (size_t)b * M * 3);
-}
-
-// gy[i] = sum_b gy[b * len + i] in ascending b, in place (row 0 receives the sum); ag_cost.hip has the same kernel private to its unit, whose code
-// object this change leaves as it is
-__global__ __launch_bounds__(256) void emd_sum_rows_kernel(float *gy, int B, int len)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= len) return;
-    float s = gy[i];
-    for (int b = 1; b < B; ++b) s += gy[(size_t)b * len + i];
-    gy[i] = s;
 }
 
 // ---- hausdorff: per sample max_n min_m c and max_m min_n c with the points that attain them ----
@@ -355,15 +338,15 @@ int ag_launch_emd_backward(const float *x, const float *y, const int *col, const
                            float *gx, float *gy, hipStream_t s)
 {
     hipLaunchKernelGGL(emd_bwd_kernel, dim3(B), dim3(256), 0, s, x, y, col, row, grad_out, N, M, y_batched, gx, gy);
-    if (gy && !y_batched && B > 1) hipLaunchKernelGGL(emd_sum_rows_kernel, dim3((3 * M + 255) / 256), dim3(256), 0, s, gy, B, 3 * M);
+    ag_launch_sum_rows(gy, B, 3 * M, y_batched, s);
     return 0;
 }
 
 int ag_launch_hausdorff(const float *x, const float *y, const unsigned char *xmask, const unsigned char *ymask, int B, int N, int M, int y_batched,
                         float *out, int *arg, hipStream_t s)
 {
+    if (!ag_cloud_resident(N, M)) return -1;              // both clouds of a sample in LDS
     const size_t smem = (size_t)3 * ((size_t)N + (size_t)M) * sizeof(float);
-    if (smem > 150 * 1024) return -1;                     // ag_chamfer's limit: both clouds of a sample in LDS
     if (smem > 48 * 1024 &&
         hipFuncSetAttribute(reinterpret_cast<const void *>(hausdorff_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem) != hipSuccess)
         return -2;

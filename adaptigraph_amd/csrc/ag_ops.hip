@@ -4,15 +4,45 @@
 
 extern "C" {
 
+// ---- the cloud-distance operators: what their entry points check alike, before anything is launched ----
+// have_all: every pointer the call cannot do without is there; masks come as a pair or not at all
+static int cloud_pointers(const char *who, bool have_all, const uint8_t *xm, const uint8_t *ym)
+{
+    if (!have_all) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
+    if ((xm == nullptr) != (ym == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    return AG_OK;
+}
+
+static int cloud_sizes(const char *who, int B, int N, int M)
+{
+    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    return AG_OK;
+}
+
+static int cloud_args(const char *who, bool have_all, const uint8_t *xm, const uint8_t *ym, int B, int N, int M)
+{
+    if (int rc = cloud_pointers(who, have_all, xm, ym)) return rc;
+    return cloud_sizes(who, B, N, M);
+}
+
+static int cloud_launched()      // behind a launcher that took the call
+{
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+static int over_resident_limit(const char *who, int N, int M)
+{
+    return ag_fail(AG_ERR_ARG, "%s: N + M = %lld exceeds the LDS-resident limit (%d points)", who, (long long)N + M, kCloudResidentPoints);
+}
+
 static int chamfer_common(const char *who, const float *x, const uint8_t *xm, const float *y, const uint8_t *ym, int B, int N, int M,
                           int y_batched, float *out, ag_stream_t stream)
 {
-    if (!x || !y || !out) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (int rc = cloud_args(who, x && y && out, xm, ym, B, N, M)) return rc;
     if (ag_launch_chamfer(x, y, xm, ym, B, N, M, y_batched ? 1 : 0, out, static_cast<hipStream_t>(stream)) != 0)
-        return ag_fail(AG_ERR_ARG, "%s: N + M = %d exceeds the LDS-resident limit (12800 points)", who, N + M);
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+        return over_resident_limit(who, N, M);
+    return cloud_launched();
 }
 
 int ag_chamfer(const float *x, const float *y, int B, int N, int M, int y_batched, float *out, ag_stream_t stream)
@@ -31,27 +61,21 @@ int ag_chamfer_fwd_idx(const float *x, const uint8_t *x_mask, const float *y, co
                        float *out, int32_t *idx_x, int32_t *idx_y, ag_stream_t stream)
 {
     const char *who = "ag_chamfer_fwd_idx";
-    if (!x || !y || !out || !idx_x || !idx_y) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
-    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (int rc = cloud_args(who, x && y && out && idx_x && idx_y, x_mask, y_mask, B, N, M)) return rc;
     if (ag_launch_chamfer_idx(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, idx_x, idx_y, static_cast<hipStream_t>(stream)) != 0)
-        return ag_fail(AG_ERR_ARG, "%s: N + M = %d exceeds the LDS-resident limit (12800 points)", who, N + M);
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+        return over_resident_limit(who, N, M);
+    return cloud_launched();
 }
 
 int ag_chamfer_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x, const int32_t *idx_y,
                         const float *grad_out, int B, int N, int M, int y_batched, float *gx, float *gy, ag_stream_t stream)
 {
     const char *who = "ag_chamfer_backward";
-    if (!x || !y || !idx_x || !idx_y || !grad_out || !gx) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
-    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (int rc = cloud_args(who, x && y && idx_x && idx_y && grad_out && gx, x_mask, y_mask, B, N, M)) return rc;
     if (ag_launch_chamfer_backward(x, x_mask, y, y_mask, idx_x, idx_y, grad_out, B, N, M, y_batched ? 1 : 0, gx, gy,
                                    static_cast<hipStream_t>(stream)) != 0)
-        return ag_fail(AG_ERR_ARG, "%s: N + M = %d exceeds the LDS-resident limit (12800 points)", who, N + M);
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+        return over_resident_limit(who, N, M);
+    return cloud_launched();
 }
 
 // ---- the tiled chamfer: clouds of any size up to 2^24 points a side (the valid counts are float adds of 1, exact up to there) ----
@@ -70,9 +94,8 @@ size_t ag_chamfer_tiled_workspace_bytes(int B, int N, int M)
     return align_up((size_t)B * ((size_t)N + (size_t)M) * sizeof(float), 256);
 }
 
-static int chamfer_tiled_sizes(const char *who, int B, int N, int M)
+static int chamfer_tiled_sizes(const char *who, int N, int M)
 {
-    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
     if (N > kChamMaxPoints || M > kChamMaxPoints) return ag_fail(AG_ERR_ARG, "%s: N=%d M=%d exceed %d points a side", who, N, M, kChamMaxPoints);
     return AG_OK;
 }
@@ -81,17 +104,16 @@ int ag_chamfer_tiled(const float *x, const uint8_t *x_mask, const float *y, cons
                      int32_t *idx_x, int32_t *idx_y, void *ws, size_t ws_bytes, ag_stream_t stream)
 {
     const char *who = "ag_chamfer_tiled";
-    if (!x || !y || !out) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
+    if (int rc = cloud_pointers(who, x && y && out, x_mask, y_mask)) return rc;
     if ((idx_x == nullptr) != (idx_y == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both index outputs or neither", who);
-    if (int rc = chamfer_tiled_sizes(who, B, N, M)) return rc;
+    if (int rc = cloud_sizes(who, B, N, M)) return rc;
+    if (int rc = chamfer_tiled_sizes(who, N, M)) return rc;
     const size_t need = ag_chamfer_tiled_workspace_bytes(B, N, M);
     if (!ws || ws_bytes < need) return ag_fail(AG_ERR_WS, "%s: workspace %zu < %zu bytes", who, ws ? ws_bytes : (size_t)0, need);
     float *near = static_cast<float *>(ws);
     if (ag_launch_chamfer_tiled(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, idx_x, idx_y, near, static_cast<hipStream_t>(stream)) != 0)
         return ag_fail(AG_ERR_ARG, "%s: B=%d samples of %d + %d points need more workgroups than one launch holds", who, B, N, M);
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+    return cloud_launched();
 }
 
 int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, const int32_t *idx_x,
@@ -99,14 +121,12 @@ int ag_chamfer_tiled_backward(const float *x, const uint8_t *x_mask, const float
                               ag_stream_t stream)
 {
     const char *who = "ag_chamfer_tiled_backward";
-    if (!x || !y || !idx_x || !idx_y || !grad_out || !gx) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
-    if (int rc = chamfer_tiled_sizes(who, B, N, M)) return rc;
+    if (int rc = cloud_args(who, x && y && idx_x && idx_y && grad_out && gx, x_mask, y_mask, B, N, M)) return rc;
+    if (int rc = chamfer_tiled_sizes(who, N, M)) return rc;
     if (ag_launch_chamfer_tiled_backward(x, x_mask, y, y_mask, idx_x, idx_y, grad_out, B, N, M, y_batched ? 1 : 0, gx, gy,
                                          static_cast<hipStream_t>(stream)) != 0)
         return ag_fail(AG_ERR_ARG, "%s: B=%d samples of %d + %d points need more workgroups than one launch holds", who, B, N, M);
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+    return cloud_launched();
 }
 
 // ---- the matching losses (ag_match.hip) ----
@@ -116,42 +136,34 @@ int ag_emd(const float *x, const uint8_t *x_mask, const float *y, const uint8_t 
            int32_t *col, int32_t *row, ag_stream_t stream)
 {
     const char *who = "ag_emd";
-    if (!x || !y || !out || !col || !row) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
-    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (int rc = cloud_args(who, x && y && out && col && row, x_mask, y_mask, B, N, M)) return rc;
     if (N > AG_EMD_MAX_POINTS || M > AG_EMD_MAX_POINTS)
         return ag_fail(AG_ERR_ARG, "%s: N=%d M=%d exceed AG_EMD_MAX_POINTS = %d points a side", who, N, M, AG_EMD_MAX_POINTS);
     if (ag_launch_emd(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, col, row, static_cast<hipStream_t>(stream)) != 0)
         return ag_fail(AG_ERR_ARG, "%s: bad sizes N=%d M=%d", who, N, M);
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+    return cloud_launched();
 }
 
 int ag_emd_backward(const float *x, const float *y, const int32_t *col, const int32_t *row, const float *grad_out, int B, int N, int M, int y_batched,
                     float *gx, float *gy, ag_stream_t stream)
 {
     const char *who = "ag_emd_backward";
-    if (!x || !y || !col || !row || !grad_out || !gx) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
+    if (int rc = cloud_args(who, x && y && col && row && grad_out && gx, nullptr, nullptr, B, N, M)) return rc;
     if (N > AG_EMD_MAX_POINTS || M > AG_EMD_MAX_POINTS)
         return ag_fail(AG_ERR_ARG, "%s: N=%d M=%d exceed AG_EMD_MAX_POINTS = %d points a side", who, N, M, AG_EMD_MAX_POINTS);
     ag_launch_emd_backward(x, y, col, row, grad_out, B, N, M, y_batched ? 1 : 0, gx, gy, static_cast<hipStream_t>(stream));
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+    return cloud_launched();
 }
 
 int ag_hausdorff(const float *x, const uint8_t *x_mask, const float *y, const uint8_t *y_mask, int B, int N, int M, int y_batched, float *out,
                  int32_t *arg, ag_stream_t stream)
 {
     const char *who = "ag_hausdorff";
-    if (!x || !y || !out || !arg) return ag_fail(AG_ERR_ARG, "%s: null argument", who);
-    if ((x_mask == nullptr) != (y_mask == nullptr)) return ag_fail(AG_ERR_ARG, "%s: give both masks or neither", who);
-    if (B < 1 || N < 1 || M < 1) return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d N=%d M=%d", who, B, N, M);
-    if ((long long)N + M > 12800) return ag_fail(AG_ERR_ARG, "%s: N + M = %lld exceeds the LDS-resident limit (12800 points)", who, (long long)N + M);
+    if (int rc = cloud_args(who, x && y && out && arg, x_mask, y_mask, B, N, M)) return rc;
+    if (!ag_cloud_resident(N, M)) return over_resident_limit(who, N, M);
     if (ag_launch_hausdorff(x, y, x_mask, y_mask, B, N, M, y_batched ? 1 : 0, out, arg, static_cast<hipStream_t>(stream)) != 0)
         return ag_fail(AG_ERR_HIP, "%s: the kernel's LDS size was refused", who);
-    AG_HIP(hipGetLastError());
-    return AG_OK;
+    return cloud_launched();
 }
 
 // ---- the planner's trajectory cost (ag_plan_cost.hip) ----

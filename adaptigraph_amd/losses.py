@@ -30,6 +30,19 @@ def _chamfer_tiled(x, xm, y, ym, y_batched, idx_x=None, idx_y=None):
     return out
 
 
+def _cloud_backward(name, head, x, y, y_batched, grad_out, want_y):
+    """The backward call of `_Chamfer` and `_Emd`: entry point `name`, `head` its arguments before grad_out -> gx, gy (None unless wanted).
+    A broadcast y (B > 1, one cloud): the kernels write one row per sample and sum them into row 0, which is what comes back."""
+    B, N, M = x.shape[0], x.shape[1], y.shape[1]
+    g = grad_out.contiguous().float()
+    gx = torch.empty_like(x)
+    gy = torch.empty((B, M, 3), dtype=torch.float32, device=x.device) if want_y else None
+    _lib.call(name, x.device, *head, g, B, N, M, y_batched, gx, gy)
+    if want_y and y.shape[0] != B:
+        gy = gy[:1]
+    return gx, gy
+
+
 class _Chamfer(torch.autograd.Function):
     """chamfer with a backward: `ag_chamfer_fwd_idx` (the same value bits as ag_chamfer / ag_chamfer_masked, plus the nearest-neighbour index
     of every point) and `ag_chamfer_backward` (gather form, no atomics: the gradient is the same bits on every call).  x (B,N,3) and y (B|1,M,3)
@@ -56,15 +69,8 @@ class _Chamfer(torch.autograd.Function):
     def backward(ctx, grad_out):
         x, y, idx_x, idx_y = ctx.saved_tensors
         xm, ym = ctx.masks
-        B, N, M = x.shape[0], x.shape[1], y.shape[1]
-        want_y = ctx.needs_input_grad[1]
-        g = grad_out.contiguous().float()
-        gx = torch.empty_like(x)
-        gy = torch.empty((B, M, 3), dtype=torch.float32, device=x.device) if want_y else None      # (a broadcast y: per-sample rows, summed into row 0)
-        _lib.call("ag_chamfer_tiled_backward" if ctx.tiled else "ag_chamfer_backward", x.device, x, xm, y, ym, idx_x, idx_y, g, B, N, M,
-                  ctx.y_batched, gx, gy)
-        if want_y and y.shape[0] != B:
-            gy = gy[:1]
+        gx, gy = _cloud_backward("ag_chamfer_tiled_backward" if ctx.tiled else "ag_chamfer_backward", (x, xm, y, ym, idx_x, idx_y), x, y,
+                                 ctx.y_batched, grad_out, ctx.needs_input_grad[1])
         return gx, gy, None, None, None
 
 
@@ -204,14 +210,7 @@ class _Emd(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out, _gcol, _grow):
         x, y, col, row = ctx.saved_tensors
-        B, N, M = x.shape[0], x.shape[1], y.shape[1]
-        want_y = ctx.needs_input_grad[1]
-        g = grad_out.contiguous().float()
-        gx = torch.empty_like(x)
-        gy = torch.empty((B, M, 3), dtype=torch.float32, device=x.device) if want_y else None      # (a broadcast y: per-sample rows, summed into row 0)
-        _lib.call("ag_emd_backward", x.device, x, y, col, row, g, B, N, M, ctx.y_batched, gx, gy)
-        if want_y and y.shape[0] != B:
-            gy = gy[:1]
+        gx, gy = _cloud_backward("ag_emd_backward", (x, y, col, row), x, y, ctx.y_batched, grad_out, ctx.needs_input_grad[1])
         return gx, gy, None, None, None
 
 
