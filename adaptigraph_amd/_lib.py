@@ -126,6 +126,14 @@ SIGNATURES = {
     # farthest-point sampling
     "ag_fps_workspace_bytes": (c_size_t, [c_int] * 2),
     "ag_fps": (c_int, [c_void_p] * 3 + [c_int] * 4 + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    # the tabletop cloud from depth images
+    "ag_tabletop_workspace_bytes": (c_size_t, [c_int]),
+    "ag_depth_cloud": (c_int, [c_void_p] * 4 + [c_int] * 4 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "ag_cloud_voxel_keys": (c_int, [c_void_p] * 2 + [c_int, P(c_double)] + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "ag_cloud_voxel_merge": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "ag_cloud_knn_mean": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "ag_cloud_outlier_filter": (c_int, [c_void_p] * 2 + [c_int, c_void_p, P(c_double)] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "ag_cloud_select": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
     # training batches assembled on the device
     "ag_gather_clouds": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3),
     "ag_assemble_batch": (c_int, [P(BatchDims)] + [c_void_p] * 8 + [P(BatchOut), c_void_p]),

@@ -110,3 +110,44 @@ def make_mpc_inputs(material, n_obj, bsz, n_look=1, seed=0, len_lo=2, len_hi=6, 
     act[..., 2] = rng.uniform(-3.14, 3.14, (bsz, n_look))
     act[..., 3] = rng.uniform(len_lo, len_hi, (bsz, n_look))
     return obj, act
+
+
+def tabletop_scene(n_cam=4, H=720, W=1280, seed=0, band=0.015, noise=0.0008, speckle=0.005):
+    """Depth images of a board (z = 0 in the board frame, 0.8 x 0.6 m) with a rope-like object (a 12 mm high ridge along y = 0.1 sin(8 x)),
+    seen by `n_cam` cameras above the board's corners looking at its centre, for adaptigraph_amd.perception: range noise, `speckle` of the
+    pixels pulled towards the camera (flying pixels), as many holes (0) and a few NaNs, and per camera the keep-mask a segmentation would give
+    (the object's neighbourhood of half-width `band`, plus a few stray pixels).
+    -> dict(depth [H,W] float32 list, masks [H,W] bool list, R, t, intr lists (camera -> board), bbox (3,2))."""
+    rng = np.random.default_rng(seed)
+    corners = [(0.55, 0.45), (-0.55, 0.45), (-0.55, -0.45), (0.55, -0.45)]
+    K = np.array([[0.9 * W, 0.0, W / 2.0], [0.0, 0.9 * W, H / 2.0], [0.0, 0.0, 1.0]])
+    Kinv = np.linalg.inv(K)
+    u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
+    rays_cam = np.stack([Kinv[r, 0] * u + Kinv[r, 1] * v + Kinv[r, 2] for r in range(3)], -1)        # z component 1: depth = z_cam
+    out = dict(depth=[], masks=[], R=[], t=[], intr=[], bbox=np.array([[-0.35, 0.35], [-0.25, 0.25], [-0.02, 0.15]]))
+    for c in range(n_cam):
+        cx, cy = corners[c % 4]
+        pos = np.array([cx, cy, 0.7 + 0.03 * (c // 4)])
+        f = -pos / np.linalg.norm(pos)
+        r = np.cross(f, [0.0, 0.0, 1.0])
+        r /= np.linalg.norm(r)
+        R = np.stack([r, np.cross(f, r), f], 1)
+        rays = rays_cam @ R.T
+        with np.errstate(divide="ignore", invalid="ignore"):
+            d0 = -pos[2] / rays[..., 2]
+            hit = pos + d0[..., None] * rays
+            near = np.abs(hit[..., 1] - 0.1 * np.sin(8.0 * hit[..., 0])) < 0.006
+            near &= np.abs(hit[..., 0]) < 0.3
+            d = np.where(near, (0.012 - pos[2]) / rays[..., 2], d0)
+            hit = pos + d[..., None] * rays
+        d = d + rng.normal(0.0, noise, d.shape)
+        pick = rng.random(d.shape)
+        d = np.where(pick < speckle, d * rng.uniform(0.5, 0.98, d.shape), d)
+        d = np.where((pick >= speckle) & (pick < 2 * speckle), 0.0, d)
+        d = np.where((pick >= 2 * speckle) & (pick < 2.1 * speckle), np.nan, d)
+        d = np.where((d0 > 0) & (d0 < 3.0), d, 0.0)
+        mask = (np.abs(hit[..., 1] - 0.1 * np.sin(8.0 * hit[..., 0])) < band) & (np.abs(hit[..., 0]) < 0.3 + band)
+        mask |= rng.random(d.shape) < 0.002
+        out["depth"].append(d.astype(np.float32)); out["masks"].append(mask)
+        out["R"].append(R); out["t"].append(pos); out["intr"].append(K.copy())
+    return out

@@ -466,6 +466,48 @@ size_t ag_fps_workspace_bytes(int B, int N);
 int ag_fps(const float *pts, const int32_t *count, const int32_t *start, int B, int N, int K, int metric, const double *radius,
            int32_t *idx, int32_t *n_out, void *workspace, size_t workspace_bytes, ag_stream_t stream);
 
+/* ---- the tabletop cloud from depth images (src/planning/perception.py:151-256, the geometry in front of get_state_cur): un-project + board
+ * frame + crop, voxel merge, the statistical outlier filter and the height filter, each ending in one ORDERED compaction (input order, no
+ * atomics decide a position).  The arithmetic is restated in adaptigraph_amd/perception.py (the host statement; the open3d details it lists
+ * were written down from memory) and repeated here operation for operation: float64 on float32 inputs, products and sums rounded separately.
+ * A cloud is pts (n_max, 3) fp32 plus a DEVICE count (its first *count rows are valid; launches are sized by n_max >= *count); 1 <= n_max <=
+ * AG_TABLETOP_MAX_POINTS, larger clouds are refused (AG_ERR_ARG).  Every call takes ag_tabletop_workspace_bytes(n_max) bytes of scratch
+ * (AG_ERR_WS otherwise; 0 = n_max out of range), free for reuse after the call's launches.  Output clouds have n_max rows and must not alias
+ * the input.  No host synchronisation, counts are device words written by kernels: safe to capture.
+ *
+ * ag_depth_cloud: depth (C,H,W) fp32, mask (C,H,W) bytes or NULL, cams (C,21) doubles = Kinv (3x3 row-major, the inverse intrinsics computed by
+ *   the caller), R (3x3), t (3); limits (8) doubles = depth lo, hi, then the box as min, max per axis.  Pixels (v, u) = (0, stride, ...): kept iff
+ *   lo < d < hi (the float widened to double), the mask byte is non-zero and the board-frame point lies in the box (inclusive; a NaN fails);
+ *   a = u d, b = v d, p_cam_r = (Kinv[r,0] a + Kinv[r,1] b) + Kinv[r,2] d, p_r = ((R[r,0] p_cam_0 + R[r,1] p_cam_1) + R[r,2] p_cam_2) + t_r, stored
+ *   as fp32, camera-major then row-major.  pts has C ceil(H/stride) ceil(W/stride) rows (that product is the call's n_max).
+ * ag_cloud_voxel_keys / ag_cloud_voxel_merge: keys[i] = the packed voxel key of point i, floor((p - origin) / voxel) per axis with origin =
+ *   min - 0.5 voxel (AG_TABLETOP_VOXEL_KEY_LIMIT keys per axis; *status = 1 if the cloud is wider), INT64_MAX behind the count.  The caller sorts
+ *   the keys STABLY (sorted_keys, perm = the source positions, int64); merge then writes one point per voxel — the sum of its members in
+ *   ascending index / their number, as fp32 — ordered by lowest member index.  voxel_size is a HOST double.
+ * ag_cloud_knn_mean: avg[i] = (sum of sqrt(d2) over the k' = min(k, *count) nearest points under the total order (d2, j), i itself included, in
+ *   ascending order) / k', d2 = (dx dx + dy dy) + dz dz; 1 <= k <= AG_TABLETOP_MAX_NEIGHBORS.  Uniform grid, ring by ring; points still
+ *   unresolved at the ring limit are finished by a brute-force pass.  info (2) = [points that took that pass, grid cells].
+ * ag_cloud_outlier_filter: mean = (sum of the avg_i > 0) / n, std = sqrt(sum over avg_i > 0 of (avg_i - mean)^2 / (n - 1)), threshold = mean +
+ *   *std_ratio std (a HOST double), sums in a fixed order; stats (3) = [mean, std, threshold]; keep[i] = 0 < avg_i < threshold (n <= 1: none);
+ *   out = the kept points; count_out (2) = [their number, the same number bit-complemented (~) when nothing was removed].
+ * ag_cloud_select: out = the points whose flags byte is non-zero, or — flags NULL — whose z is < *z_below (a device float); exactly one of them. */
+#define AG_TABLETOP_MAX_POINTS (1 << 20)
+#define AG_TABLETOP_MAX_NEIGHBORS 20
+#define AG_TABLETOP_VOXEL_KEY_LIMIT (1 << 21)
+size_t ag_tabletop_workspace_bytes(int n_max);
+int ag_depth_cloud(const float *depth, const uint8_t *mask, const double *cams, const double *limits, int C, int H, int W, int stride, float *pts,
+                   int32_t *count, void *workspace, size_t workspace_bytes, ag_stream_t stream);
+int ag_cloud_voxel_keys(const float *pts, const int32_t *count, int n_max, const double *voxel_size, int64_t *keys, int32_t *status,
+                        void *workspace, size_t workspace_bytes, ag_stream_t stream);
+int ag_cloud_voxel_merge(const float *pts, const int32_t *count, int n_max, const int64_t *sorted_keys, const int64_t *perm, float *out,
+                         int32_t *count_out, void *workspace, size_t workspace_bytes, ag_stream_t stream);
+int ag_cloud_knn_mean(const float *pts, const int32_t *count, int n_max, int k, double *avg, int32_t *info, void *workspace,
+                      size_t workspace_bytes, ag_stream_t stream);
+int ag_cloud_outlier_filter(const float *pts, const int32_t *count, int n_max, const double *avg, const double *std_ratio, double *stats,
+                            uint8_t *keep, float *out, int32_t *count_out, void *workspace, size_t workspace_bytes, ag_stream_t stream);
+int ag_cloud_select(const float *pts, const int32_t *count, int n_max, const uint8_t *flags, const float *z_below, float *out, int32_t *count_out,
+                    void *workspace, size_t workspace_bytes, ag_stream_t stream);
+
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
  *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
