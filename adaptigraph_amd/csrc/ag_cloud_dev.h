@@ -5,6 +5,7 @@
 // Arithmetic of a pair: d2 = (dx dx + dy dy) + dz dz in fp32 with separately rounded products (-ffp-contract=off: what torch's
 // ((x - y) ** 2).sum(-1) computes), cost = sqrtf(d2), u(v) = v / ||v|| with u(0) = 0.
 #pragma once
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 typedef float ag_f2 __attribute__((ext_vector_type(2)));
@@ -39,22 +40,7 @@ __device__ __forceinline__ CloudSample cloud_sample(const float *x, const float 
     return {x + (size_t)b * N * 3, y + (size_t)by * M * 3, xmask ? xmask + (size_t)b * N : nullptr, ymask ? ymask + (size_t)by * M : nullptr};
 }
 
-// ---- four-wave reduction tail of a 256-thread workgroup ----
-// K per-thread partial sums (or counts): the xor-shuffle tree of every wave, lane 0 parks wave w's sums in red[k][w].  After a barrier,
-// four_wave_total(red[k]) is the workgroup's sum, added as (w0 + w1) + (w2 + w3).
-template <int K>
-__device__ __forceinline__ void four_wave_park(float (&v)[K], float (*red)[4], int lane, int wave)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int k = 0; k < K; ++k) v[k] += __shfl_xor(v[k], o);
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[k][wave] = v[k];
-}
-__device__ __forceinline__ float four_wave_total(const float *r) { return (r[0] + r[1]) + (r[2] + r[3]); }
-
+// ---- the four-wave reduction tail (four_wave_park / four_wave_total: ag_block_dev.h) of the chamfer kernels ----
 // the chamfer value of a sample from the parked {sum_y, sum_x, n_y, n_x}: the two means; NaN when a side has no valid point
 __device__ __forceinline__ float chamfer_value(const float (*red)[4])
 {

@@ -11,6 +11,7 @@
 //
 // Launches: zero the B*N counters | row scan (one wave per row pair: keys + counts) | two-pass scan of the counts -> row_ptr | stable placement
 // (one wave per sample walks its E keys in order).  Integer atomics only.
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 namespace {
@@ -88,28 +89,7 @@ __global__ __launch_bounds__(256) void dense_rows_kernel(const float *Rr, const 
     }
 }
 
-// ---- counts -> row_ptr: the builder's two-pass scan (ag_edges.hip: scan_partial_kernel / rowptr_scatter_kernel), 256 rows per workgroup
-constexpr int kScanRows = 256;
-
-__device__ int block_exclusive_scan(int v, int *total)
-{
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return base + x - v;
-}
-
+// ---- counts -> row_ptr: the two-pass scan of ag_block_dev.h, kScanRows rows per workgroup
 __global__ __launch_bounds__(256) void dense_count_partial_kernel(const int32_t *cnt, int rows, int32_t *blk_sum)
 {
     const long long r = (long long)blockIdx.x * kScanRows + threadIdx.x;      // (64 bits: B N may sit right under 2^31)
@@ -121,10 +101,7 @@ __global__ __launch_bounds__(256) void dense_count_partial_kernel(const int32_t 
 // every block adds up the partial sums in front of it itself; `cnt` goes from a row's count to its first output position (the placement's cursor)
 __global__ __launch_bounds__(256) void dense_rowptr_kernel(int32_t *cnt, int rows, const int32_t *blk_sum, int32_t *row_ptr)
 {
-    int part = 0;
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) part += blk_sum[i];
-    int base;
-    block_exclusive_scan(part, &base);
+    const int base = block_offset(blk_sum);
     const long long r = (long long)blockIdx.x * kScanRows + threadIdx.x;
     int total;
     const int off = base + block_exclusive_scan(r < rows ? cnt[r] : 0, &total);
@@ -163,7 +140,7 @@ __global__ __launch_bounds__(64) void dense_place_kernel(const int32_t *key_recv
             if (lane == leader)      // (an atomic for its return value and its ordering; one wave, no contention)
                 first = LDS ? atomicAdd(&s_cur[kk], __popcll(m)) : atomicAdd(&g_cur[kk], __popcll(m));
             first = __shfl(first, leader);
-            const long long pos = (long long)first + __popcll(m & ((1ull << lane) - 1ull));
+            const long long pos = (long long)first + ballot_rank(m, lane);
             if (k == kk && pos >= 0 && pos < cap) {
                 edge_recv[pos] = g0 + kk;
                 edge_send[pos] = g0 + sd;

@@ -1,6 +1,7 @@
 // ag_drivers.hip — the rollout drivers of the C ABI: ag_rollout (round-robin or CU-partitioned scheduler), its shared-state form, ag_rollout_ragged
 // (either form on one stream, every model step sized for the samples still running) and ag_rollout_scripted; each carves its lanes, binds a step's
 // arguments once and runs the engine's kernel sequence (ag_engine.hip) per model step.
+#include "ag_block_dev.h"
 #include "ag_host.h"
 
 static_assert(AG_ORDER_STEPS == AG_RAGGED_MAX_STEPS && AG_STATUS_ORDER_BIT == AG_STATUS_ORDER, "the kernels' constants are the header's");
@@ -206,8 +207,8 @@ static void carve_shared(Carver &c, const ag_model *m, const ag_rollout_params *
     s.send_o = c.take<int32_t>(ecoo);
     s.send_r0 = c.take<int32_t>(ecoo);
     s.send_cm = c.take<int32_t>(ecoo);
-    s.blk_cnt = c.take<int32_t>(rows / 256 + 2);
-    s.blk_deg = c.take<int32_t>(rows / 256 + 2);
+    s.blk_cnt = c.take<int32_t>(ag_scan_blocks(rows));
+    s.blk_deg = c.take<int32_t>(ag_scan_blocks(rows));
     s.n_rows = c.take<int>(4);
     s.n_edges = s.n_rows + 1;
     carve_step(c, l, p, B1, N, true, eterm16, true);

@@ -15,6 +15,7 @@
 //   connect_tools_all : the two variants' override rules, including the batch variant's per-sample
 //           batch_mask and the tool->tool edges it keeps (graph.py:77-80 vs :134-144)
 //   order : (receiver, sender) ascending == adj_matrix.nonzero() row-major order (graph.py:151)
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 namespace {
@@ -56,7 +57,7 @@ __device__ int prune_topk(float *cd, int *cj, int cnt, int k, int lane)
         const unsigned long long bal = __ballot(keep);
         wave_lds_fence();   // all lanes hold their (d, j) before anyone overwrites a slot
         if (keep) {
-            const int pos = newcnt + __popcll(bal & ((1ull << lane) - 1ull));
+            const int pos = newcnt + ballot_rank(bal, lane);
             cd[pos] = d;
             cj[pos] = jj;
         }
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(256) void select_kernel(AgEdgeArgs a)
                     cnt = prune_topk(cd, cj, cnt, k, lane);
                 }
                 if (c) {
-                    const int p = cnt + __popcll(bal & ((1ull << lane) - 1ull));
+                    const int p = cnt + ballot_rank(bal, lane);
                     cd[p] = d;
                     cj[p] = j;
                 }
@@ -134,25 +135,6 @@ __global__ __launch_bounds__(256) void select_kernel(AgEdgeArgs a)
         }
         wave_lds_fence();
     }
-}
-
-__device__ int block_exclusive_scan(int v, int *total)
-{
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    __syncthreads();
-    return base + x - v;
 }
 
 // ---- uniform-grid ("cell list") candidate search -------------------------------------------------------------
@@ -362,7 +344,7 @@ __global__ __launch_bounds__(256) void select_cells_kernel(AgEdgeArgs a)
                 if (bal) {
                     if (cnt + 64 > kCand) cnt = prune_topk(cd, cj, cnt, k, lane);
                     if (c) {
-                        const int q = cnt + __popcll(bal & ((1ull << lane) - 1ull));
+                        const int q = cnt + ballot_rank(bal, lane);
                         cd[q] = d;
                         cj[q] = j;
                     }
@@ -642,7 +624,7 @@ __global__ __launch_bounds__(256) void finalize_connect_kernel(AgEdgeArgs a)
 #pragma unroll
         for (int u = 0; u < kFlagK; ++u)
             if (tflag >> u & 1u) {
-                const int slot = wbase[u][wave] + __popcll(bal[u] & ((1ull << lane) - 1ull));
+                const int slot = wbase[u][wave] + ballot_rank(bal[u], lane);
                 if (slot < a.cap) tools[slot] = tid + 256 * u;      // only the first `cap` tools can reach a (cap-long) output row
             }
         nt = s_total;
@@ -656,7 +638,7 @@ __global__ __launch_bounds__(256) void finalize_connect_kernel(AgEdgeArgs a)
         __syncthreads();
         int base = nt;
         for (int w = 0; w < wave; ++w) base += wcount[w];
-        const int slot = base + __popcll(bal & ((1ull << lane) - 1ull));
+        const int slot = base + ballot_rank(bal, lane);
         if (t && slot < a.cap) tools[slot] = j;      // only the first `cap` tools can reach a (cap-long) output row
         nt += wcount[0] + wcount[1] + wcount[2] + wcount[3];
         __syncthreads();
@@ -726,7 +708,7 @@ __global__ __launch_bounds__(256) void finalize_connect_sweep_kernel(AgEdgeArgs 
         if (add_tools && tj) member = true;
         const unsigned long long bal = __ballot(member);
         if (member) {
-            const int p = out + __popcll(bal & ((1ull << lane) - 1ull));
+            const int p = out + ballot_rank(bal, lane);
             if (p < a.cap) a.sel[row * a.cap + p] = j;
         }
         out += __popcll(bal);
@@ -734,8 +716,7 @@ __global__ __launch_bounds__(256) void finalize_connect_sweep_kernel(AgEdgeArgs 
     if (lane == 0) a.deg[row] = out < a.cap ? out : a.cap;
 }
 
-// ---- exclusive scan of the per-row degrees -> row_ptr, then COO fill -----------------------------
-constexpr int kScanRows = 256;    // rows per block (one per thread; ag_engine.hip sizes blk_sum with the same number)
+// ---- exclusive scan of the per-row degrees -> row_ptr (the two-pass scan of ag_block_dev.h: kScanRows rows per block), then COO fill ----
 
 // Self-edge elision (AgEdgeArgs::self_attrs): a row's self-loop is left out of the lists when the node's attribute pair is class 0 / 1
 // (ag_self_class).  Its position in the (ascending) sender row is found here — the workgroup's 256 rows staged through LDS with coalesced
@@ -818,10 +799,7 @@ __global__ __launch_bounds__(256) void rowptr_scatter_kernel(AgEdgeArgs a, const
     // (The overflow word is read here, with the partial sums, not in front of the loop that uses it: one memory round trip less on the chain.)
     const bool map = a.map_send_c != nullptr;
     const bool ident = map && *a.map_ovf != 0;          // the call overflowed the compact tables: round 0 gathers the full-size table by node id
-    int part = 0;
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) part += a.blk_sum[i];
-    int base;
-    block_exclusive_scan(part, &base);
+    const int base = block_offset(a.blk_sum);
     const int r = blockIdx.x * kScanRows + threadIdx.x;
     const bool live = r < rows && !(a.active && !a.active[r / a.N]);      // (rows of a skipped sample: degree 0, nothing of theirs is read — not even self_pos,
     const int d = live ? a.deg[r] : 0;                                    //  which the degree scan's early-exit blocks never wrote)

@@ -1,5 +1,6 @@
 // ag_engine.hip — one model step on the host: workspace layouts, the call's kernel path and arguments, the kernel sequence; and the entry points
 // that are one such step or one edge build (ag_forward, ag_build_edges, dense <-> CSR).  The rollout drivers (ag_drivers.hip) run the same sequence.
+#include "ag_block_dev.h"
 #include "ag_host.h"
 
 #include <algorithm>
@@ -59,7 +60,7 @@ void carve_edges(Carver &c, AgEdgeArgs &a)
     a.sel = a.connect ? c.take<int32_t>(rows * a.cap) : nullptr;
     a.deg = c.take<int32_t>(rows);
     a.flag = c.take<int32_t>(a.B);
-    a.blk_sum = c.take<int32_t>(rows / 256 + 2);       // one partial sum per 256 rows (ag_edges.hip: kScanRows)
+    a.blk_sum = c.take<int32_t>(ag_scan_blocks(rows));
     a.grid_raw = c.take<int32_t>((size_t)a.B * 8);
     a.cell_start = c.take<int32_t>((size_t)a.B * 8193);
     a.sorted = c.take<float4>(rows);
@@ -71,7 +72,7 @@ static void carve_dense(Carver &c, AgDenseArgs &a)
     a.key_recv = c.take<int32_t>(pairs);
     a.key_send = c.take<int32_t>(pairs);
     a.cnt = c.take<int32_t>(rows);
-    a.blk_sum = c.take<int32_t>(rows / 256 + 2);       // one partial sum per 256 receivers (ag_dense.hip: kScanRows)
+    a.blk_sum = c.take<int32_t>(ag_scan_blocks(rows));
 }
 
 void edge_caps(int N, int topk, int connect, int max_tools, int *cap0, int *cap)

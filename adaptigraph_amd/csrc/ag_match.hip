@@ -53,7 +53,7 @@ __device__ __forceinline__ int compact_valid(const float *p, const unsigned char
         const bool v = q < Q && (!mask || mask[q]);
         if (v && !finite3(p + 3 * q)) bad = true;
         const unsigned long long bal = __ballot(v);
-        if (v) list[count + __popcll(bal & ((1ull << lane) - 1ull))] = q;
+        if (v) list[count + ballot_rank(bal, lane)] = q;
         count += __popcll(bal);
         if (q < Q) marks[q] = -1;
     }
@@ -229,10 +229,10 @@ __global__ __launch_bounds__(256) void emd_bwd_kernel(const float *x, const floa
     int cnt = 0;
     for (int n = tid; n < N; n += 256) cnt += colb[n] >= 0 ? 1 : 0;
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);      // (not wave_sum: the matching kernels keep the machine code they had)
     if (lane == 0) red[wave] = cnt;
     __syncthreads();
-    const int K = (red[0] + red[1]) + (red[2] + red[3]);
+    const int K = four_wave_total(red);
     const float inv_k = K > 0 ? 1.f / (float)K : 0.f, g = grad_out[b];
     emd_bwd_side(xb, yb, colb, N, g, inv_k, tid, gx + (size_t)b * N * 3);
     if (gy) emd_bwd_side(yb, xb, rowb, M, g, inv_k, tid, gy + (size_t)b * M * 3);

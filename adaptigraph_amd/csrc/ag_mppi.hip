@@ -15,6 +15,7 @@
 // NaN: a NaN reward is the chunk's arg-max (the first one, as torch.argmax and np.argmax have it) and makes max t, so every weight and the chunk's
 // new sequence NaN (the clamp is two compares that keep one).  No other chunk reads it.
 #include "../../include/adaptigraph_hip.h"
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 #include <climits>
@@ -25,7 +26,6 @@ constexpr int kMppiThreads = 256;
 constexpr int kMppiWaves = kMppiThreads / 64;
 constexpr int kMppiU = 4;      // samples per thread held in registers, and loads in flight per thread in a later trip
 
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }      // once NaN, NaN
 __device__ __forceinline__ float clamp_keep(float v, float lo, float hi)                              // min(v, hi) then max(., lo): NaN stays
 {
     v = v > hi ? hi : v;
@@ -42,13 +42,6 @@ __device__ __forceinline__ Best better(Best p, Best q)
     const bool pn = p.v != p.v, qn = q.v != q.v;
     const bool take_q = (pn || qn) ? (qn && (!pn || q.i < p.i)) : (q.v > p.v || (q.v == p.v && q.i < p.i));
     return take_q ? q : p;
-}
-
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
 }
 
 // one action row (x, z, theta, length); the compiler makes the four words one 16-byte load

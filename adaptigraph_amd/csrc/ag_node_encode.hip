@@ -1,4 +1,5 @@
 // ag_node_encode.hip — node encoder and its de-duplication passes (shared device layer: ag_mlp_dev.h)
+#include "ag_block_dev.h"
 #include "ag_mlp_dev.h"
 
 namespace {
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(256) void node_classify_kernel(AgFwdArgs a)
                 slot0 = __shfl(slot0, first);
                 prow0 = __shfl(prow0, first);
                 if (valid && match < 0) {
-                    const int rank = __popcll(priv & ((1ull << lane) - 1ull));
+                    const int rank = ballot_rank(priv, lane);
                     row = a.shared_rows + prow0 + rank;                      // private rows follow the B x AG_DEDUP_REPS shared ones
                     const bool fits = row < a.rows_c && slot0 + rank < a.rows_c;
                     if (!fits) { *a.ovf = 1; row = a.rows_c - 1; }           // budget exhausted: this call runs without de-duplication (every consumer tests ovf)

@@ -15,8 +15,9 @@
 // table — each thread meets the rows it would meet in a call on the chunk alone, in the same order, so the chunk's rewards are that call's bits.
 //
 // NaN: torch's min / max / mean / clamp carry a NaN, fminf / fmaxf drop it.  The reductions below are written as compares that keep one
-// (nan_min / nan_max, keep_pos, cap_at), so that a diverged sample gets a NaN reward as in the reference, never a good one.
+// (nan_min / nan_max of ag_block_dev.h, keep_pos, cap_at), so that a diverged sample gets a NaN reward as in the reference, never a good one.
 #include "../../include/adaptigraph_hip.h"
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 namespace {
@@ -25,29 +26,8 @@ constexpr int kPlanWaves = 4;      // clouds per workgroup
 constexpr int kPlanU = 4;          // particles per lane in flight
 constexpr int kRewardThreads = 1024;
 
-__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }      // once NaN, NaN
-__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
 __device__ __forceinline__ float keep_pos(float v) { return v < 0.f ? 0.f : v; }                      // clamp_min(0): NaN stays
 __device__ __forceinline__ float cap_at(float v, float c) { return v > c ? c : v; }                   // clamp_max(c): NaN stays
-
-__device__ __forceinline__ float wave_min(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = nan_min(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_max(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o));
-    return v;
-}
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 struct Sweep {
     float xlo = INFINITY, xhi = -INFINITY, zlo = INFINITY, zhi = -INFINITY;
@@ -144,11 +124,11 @@ __global__ __launch_bounds__(64 * kPlanWaves) void plan_terms_kernel(const AgPla
         pusher_points<1>(act, a.rad, px, pz);
         sweep<1, false, false, true>(a.state_init, a.n, lane, px, pz, a.box, init);
     }
-    const float xlo = wave_min(own.xlo), xhi = wave_max(own.xhi), zlo = wave_min(own.zlo), zhi = wave_max(own.zhi);
+    const float xlo = wave_nan_min(own.xlo), xhi = wave_nan_max(own.xhi), zlo = wave_nan_min(own.zlo), zhi = wave_nan_max(own.zhi);
     const float box_sum = BOX ? wave_sum(own.box_sum) : 0.f;
-    const float near_next = kPush ? wave_min(own.near) : 0.f;
-    const float near_init = PEN != AG_PENALTY_NONE ? wave_min(init.near) : 0.f;
-    const float far_init = PEN == AG_PENALTY_CLOTH ? wave_max(init.far) : 0.f;
+    const float near_next = kPush ? wave_nan_min(own.near) : 0.f;
+    const float near_init = PEN != AG_PENALTY_NONE ? wave_nan_min(init.near) : 0.f;
+    const float far_init = PEN == AG_PENALTY_CLOTH ? wave_nan_max(init.far) : 0.f;
     if (lane != 0) return;
     float *t = a.terms + (size_t)c * AG_PLAN_TERMS;
     t[0] = BOX ? box_sum / (float)a.n : a.error_in[c];
@@ -189,8 +169,8 @@ __device__ __forceinline__ void plan_reward_rows(const AgPlanCostArgs &a, int b0
         emax = nan_max(emax, t[0]);
         if constexpr (CLOTH) fmax_ = nan_max(fmax_, cap_at(t[4], a.far_cap));
     }
-    emax = wave_max(emax);
-    if constexpr (CLOTH) fmax_ = wave_max(fmax_);
+    emax = wave_nan_max(emax);
+    if constexpr (CLOTH) fmax_ = wave_nan_max(fmax_);
     if (lane == 0) { red[0][wave] = emax; red[1][wave] = fmax_; }
     __syncthreads();
     emax = red[0][0];

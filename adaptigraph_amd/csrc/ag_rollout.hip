@@ -9,6 +9,7 @@
 // A sample is updated by ceil(3N / 2048) workgroups (grid.y), each of which re-derives the sample's tool height from the predicted
 // positions itself (a 4-16 KB L2-resident read: cheaper than a second launch or a grid-wide hand-off; with ONE workgroup per sample the
 // 64-sample cloth-4k launch used a quarter of the CUs: 0.077 ms); no host synchronisation (the reference syncs via .item() every step).
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 namespace {
@@ -19,7 +20,7 @@ constexpr int kStepChunk = 2048;     // plane elements per workgroup
 template <bool SHARED>
 __global__ __launch_bounds__(256) void rollout_step_kernel(AgStepArgs a)
 {
-    __shared__ float red[8];
+    __shared__ float red[2][4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // prediction of particle i, component c: by (sample, particle), or — shared-state rollout — by compact row through cmap (a private row or the base's)
     const float *pred = a.pred_pos + (SHARED ? (size_t)0 : (size_t)b * a.n_p * 3);
@@ -30,24 +31,21 @@ __global__ __launch_bounds__(256) void rollout_step_kernel(AgStepArgs a)
     if (a.height_mode == 0) {
         float m = INFINITY;
         for (int i = tid; i < a.n_p; i += 256) m = fminf(m, at(i, 1));
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) m = fminf(m, __shfl_xor(m, o));
-        if (lane == 0) red[wave] = m;
+        m = wave_fmin(m);
+        if (lane == 0) red[0][wave] = m;
         __syncthreads();
-        y = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+        y = four_wave_min(red[0]);
     } else {
         const uint8_t *mk = a.obj_mask + (size_t)b * a.n_p;
-        float s = 0.f, c = 0.f;
+        float sc[2] = {0.f, 0.f};      // masked sum of the heights, mask count
         for (int i = tid; i < a.n_p; i += 256) {
             const float w = mk[i] ? 1.f : 0.f;
-            s += at(i, 1) * w;
-            c += w;
+            sc[0] += at(i, 1) * w;
+            sc[1] += w;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); c += __shfl_xor(c, o); }
-        if (lane == 0) { red[wave] = s; red[4 + wave] = c; }
+        four_wave_park(sc, red, lane, wave);
         __syncthreads();
-        y = ((red[0] + red[1]) + (red[2] + red[3])) / ((red[4] + red[5]) + (red[6] + red[7]));
+        y = four_wave_total(red[0]) / four_wave_total(red[1]);
     }
     y += a.raise;
 

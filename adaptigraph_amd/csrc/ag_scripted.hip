@@ -9,6 +9,7 @@
 // Unlike rollout_step_kernel (ag_rollout.hip) the tool is not advanced by last + delta and has no height rule; the last step reads no script
 // entry and leaves state and action as its forward saw them.  A sample is updated by ceil(3N / 2048) workgroups (grid.y); the error sum is
 // taken by the first of them alone, in one fixed order: no atomics, no memset, no second launch, the same bits every call.
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 namespace {
@@ -17,27 +18,25 @@ constexpr int kStepChunk = 2048;     // plane elements per workgroup
 
 __global__ __launch_bounds__(256) void scripted_step_kernel(AgScriptArgs a)
 {
-    __shared__ float red[8];
+    __shared__ float red[2][4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float *pred = a.pred_pos + (size_t)b * a.n_p * 3;
     const size_t bt = (size_t)b * a.T + a.t;
 
     if (a.gt && blockIdx.y == 0) {
-        // thread: its points in ascending order; wave: xor butterfly; workgroup: the four wave sums left to right
+        // thread: its points in ascending order; wave and workgroup: the fixed order of ag_block_dev.h
         const float *g = a.gt + bt * a.n_p * 3;
         const uint8_t *mk = a.obj_mask ? a.obj_mask + (size_t)b * a.n_p : nullptr;
-        float s = 0.f, c = 0.f;
+        float sc[2] = {0.f, 0.f};      // sum of the errors, count of the points
         for (int i = tid; i < a.n_p; i += 256) {
             if (mk && !mk[i]) continue;
             const float dx = pred[i * 3] - g[i * 3], dy = pred[i * 3 + 1] - g[i * 3 + 1], dz = pred[i * 3 + 2] - g[i * 3 + 2];
-            s += sqrtf((dx * dx + dy * dy) + dz * dz);
-            c += 1.f;
+            sc[0] += sqrtf((dx * dx + dy * dy) + dz * dz);
+            sc[1] += 1.f;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); c += __shfl_xor(c, o); }
-        if (lane == 0) { red[wave] = s; red[4 + wave] = c; }
+        four_wave_park(sc, red, lane, wave);
         __syncthreads();
-        if (tid == 0) a.err[bt] = ((red[0] + red[1]) + (red[2] + red[3])) / fmaxf((red[4] + red[5]) + (red[6] + red[7]), 1.f);
+        if (tid == 0) a.err[bt] = four_wave_total(red[0]) / fmaxf(four_wave_total(red[1]), 1.f);
     }
 
     const int plane = a.N * 3, obj = a.n_p * 3;

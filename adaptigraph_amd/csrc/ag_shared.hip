@@ -15,6 +15,7 @@
 // Every row that is not private has the base's edge list, the base's inputs and only senders whose values equal the base's: its result IS the base
 // row's, and ag_rollout.hip's state update copies it from there.  Summation orders are untouched, so the rollout equals the plain one bit for bit
 // (tests/test_gpu_parity.py: test_shared_state_*).
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 namespace {
@@ -151,46 +152,25 @@ __global__ __launch_bounds__(256) void shared_hop_kernel(AgSharedArgs a, const u
     out[g] = sel ? 1 : 0;
 }
 
-__device__ int2 block_exclusive_scan2(int2 v, int2 *total)
-{
-    __shared__ int2 wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int2 x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y0 = __shfl_up(x.x, o), y1 = __shfl_up(x.y, o);
-        if (lane >= o) { x.x += y0; x.y += y1; }
-    }
-    if (lane == 63) wsum[wave] = x;
-    __syncthreads();
-    int2 base = make_int2(0, 0);
-    for (int w = 0; w < wave; ++w) { base.x += wsum[w].x; base.y += wsum[w].y; }
-    *total = make_int2(wsum[0].x + wsum[1].x + wsum[2].x + wsum[3].x, wsum[0].y + wsum[1].y + wsum[2].y + wsum[3].y);
-    __syncthreads();
-    return make_int2(base.x + x.x - v.x, base.y + x.y - v.y);
-}
-
+// the compact numbering: two scans at once (selected rows, their edges) by the two-pass scan of ag_block_dev.h
 __global__ __launch_bounds__(256) void shared_scan_partial_kernel(AgSharedArgs a, const uint8_t *sel)
 {
     const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool on = g < (long long)a.B1 * a.N && sel[g] != 0;
     int2 total;
-    block_exclusive_scan2(make_int2(on ? 1 : 0, on ? a.row_ptr[g + 1] - a.row_ptr[g] : 0), &total);
+    block_exclusive_scan(make_int2(on ? 1 : 0, on ? a.row_ptr[g + 1] - a.row_ptr[g] : 0), &total);
     if (threadIdx.x == 0) { a.blk_cnt[blockIdx.x] = total.x; a.blk_deg[blockIdx.x] = total.y; }
 }
 
 __global__ __launch_bounds__(256) void shared_offsets_kernel(AgSharedArgs a, const uint8_t *sel)
 {
-    int2 part = make_int2(0, 0);
-    for (int i = threadIdx.x; i < (int)blockIdx.x; i += 256) { part.x += a.blk_cnt[i]; part.y += a.blk_deg[i]; }
-    int2 base;
-    block_exclusive_scan2(part, &base);      // (the TOTAL of the partial sums in front of this block)
+    const int2 base = block_offset(a.blk_cnt, a.blk_deg);
     const long long g = (long long)blockIdx.x * 256 + threadIdx.x;
     const bool in = g < (long long)a.B1 * a.N;
     const bool on = in && sel[g] != 0;
     const int e0 = in ? a.row_ptr[g] : 0, d = on ? a.row_ptr[g + 1] - e0 : 0;
     int2 total;
-    const int2 ex = block_exclusive_scan2(make_int2(on ? 1 : 0, d), &total);
+    const int2 ex = block_exclusive_scan(make_int2(on ? 1 : 0, d), &total);
     if (in) {
         if (on) {
             const int c = base.x + ex.x;

@@ -8,7 +8,7 @@
 // before it addresses anything.
 //
 // Ordered compaction (crop, voxel leaders, outlier filter, height filter): a stage writes one flag byte per item and the number of set flags
-// per 256-item block (`sums`); compact_scatter_kernel then lets every block add up the sums in front of it (integers: exact in any order), ranks
+// per 256-item block (`sums`); compact_scatter_kernel then lets every block add up the sums in front of it (block_offset of ag_block_dev.h), ranks
 // its own flags by ballot + popcount and copies the flagged rows — input order, no atomics; the last block writes the new count.
 //
 // Neighbour mean: the points are counting-sorted into a uniform grid (cell edge h from the bounding box and the count: about eight points per
@@ -18,6 +18,7 @@
 // grid.  A point unresolved after kMaxRing rings is an isolated outlier: it goes onto a work list (a counter: the ORDER of that list decides
 // nothing) and is finished by brute_kernel, one wave per point over the whole cloud.  Either way the selected set and the values are those of
 // the O(n^2) scan.
+#include "ag_block_dev.h"
 #include "ag_host.h"
 
 namespace {
@@ -61,26 +62,23 @@ __global__ __launch_bounds__(kBlock) void compact_scatter_kernel(const float *__
                                                                  float *__restrict__ dst, int32_t *__restrict__ count_out,
                                                                  int32_t *__restrict__ progress)
 {
-    __shared__ int s_part[kBlock / 64], s_cnt[kBlock / 64];
+    static_assert(kBlock == kScanRows, "sums holds one count per block of the two-pass scan");
+    __shared__ int s_cnt[kBlock / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int part = 0;
-    for (int j = tid; j < b; j += kBlock) part += sums[j];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) part += __shfl_xor(part, m);
+    const int base = block_offset(sums);
     const int n = cloud_count(count, n_max), i = b * kBlock + tid;
     const bool f = i < n && flags[i] != 0;
     const u64 bal = __ballot(f);
-    if (lane == 0) { s_part[wave] = part; s_cnt[wave] = __popcll(bal); }
+    if (lane == 0) s_cnt[wave] = __popcll(bal);
     __syncthreads();
-    int base = 0, before = 0, total = 0;
+    int before = 0, total = 0;
 #pragma unroll
     for (int w = 0; w < kBlock / 64; ++w) {
-        base += s_part[w];
         before += w < wave ? s_cnt[w] : 0;
         total += s_cnt[w];
     }
     if (f) {
-        const size_t pos = (size_t)(base + before + __popcll(bal & ((1ull << lane) - 1ull)));
+        const size_t pos = (size_t)(base + before + ballot_rank(bal, lane));
         if (pos < (size_t)n_max) {
             dst[3 * pos] = src[3 * (size_t)i]; dst[3 * pos + 1] = src[3 * (size_t)i + 1]; dst[3 * pos + 2] = src[3 * (size_t)i + 2];
         }
@@ -173,9 +171,7 @@ __global__ __launch_bounds__(kWide) void bounds_kernel(const float *__restrict__
             mn[a] = fminf(mn[a], v); mx[a] = fmaxf(mx[a], v);
         }
 #pragma unroll
-    for (int a = 0; a < 3; ++a)
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], m)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], m)); }
+    for (int a = 0; a < 3; ++a) { mn[a] = wave_fmin(mn[a]); mx[a] = wave_fmax(mx[a]); }
     if ((tid & 63) == 0)
         for (int a = 0; a < 3; ++a) { s_mn[tid >> 6][a] = mn[a]; s_mx[tid >> 6][a] = mx[a]; }
     __syncthreads();
@@ -222,8 +218,7 @@ __global__ __launch_bounds__(kWide) void grid_refine_kernel(const int32_t *__res
     const int tid = threadIdx.x, ncell = max(1, min(grid->ncell, nc_max));
     int occ = 0;
     for (int c = tid; c < ncell; c += kWide) occ += cell_count[c] > 0 ? 1 : 0;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) occ += __shfl_xor(occ, m);
+    occ = wave_sum(occ);
     if ((tid & 63) == 0) s_occ[tid >> 6] = occ;
     __syncthreads();
     if (tid != 0) return;

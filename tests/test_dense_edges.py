@@ -156,6 +156,18 @@ def test_from_dense_equals_the_host_function(kind):
         assert_same_csr(got, aggraph.csr_from_dense(Rr, Rs), f"{kind} B={B} E={E} N={N}")
 
 
+@pytest.mark.gpu
+def test_from_dense_behind_more_than_256_scan_blocks():
+    """66 066 receivers are 259 scan blocks, the last one partial: the blocks behind the 256th take a second trip through the strided sum of the
+    partial sums in front of them."""
+    B, E, N = 66, 7, 1001
+    Rr, Rs = dense_case("padded", B, E, N, seed=5)
+    got = aggraph.csr_from_dense_device(Rr, Rs)
+    want = aggraph.csr_from_dense(Rr, Rs)
+    assert int(want.row_ptr[256 * 256]) > 0 and int(want.row_ptr[-1]) > int(want.row_ptr[256 * 256])      # edges on both sides of block 256
+    assert_same_csr(got, want, f"B={B} E={E} N={N}")
+
+
 def built_graphs():
     for material, n_obj, batch, kw in (("rope", 93, 5, dict(spacing=0.1, n_pad=7)), ("cloth", 256, 2, {}), ("granular", 300, 2, {}),
                                        ("rope", 5, 2, dict(spacing=10.0))):

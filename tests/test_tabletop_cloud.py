@@ -406,6 +406,26 @@ def test_height_filter_device():
 
 
 @gpu
+@pytest.mark.parametrize("fill", ["half", "none", "all"])
+def test_select_device_behind_more_than_256_blocks(fill):
+    """The last blocks of the compaction have more than 256 block sums in front of them (over 65 536 points): the second trip of the strided sum
+    in their base offset.  The count is not a multiple of 256 and lies below the bound; flag bytes other than 0 and 1 count as set."""
+    bound, n = 66013, 66001
+    rng = np.random.default_rng(17)
+    p = rng.uniform(-1, 1, (bound, 3)).astype(np.float32)
+    flags = {"half": np.where(rng.random(bound) < 0.5, rng.integers(1, 256, bound), 0), "none": np.zeros(bound), "all": np.full(bound, 7)}[fill]
+    flags = flags.astype(np.uint8)
+    assert fill != "half" or (0.45 * n < np.count_nonzero(flags[:n]) < 0.55 * n and flags.max() > 1 and flags[n:].any())
+    cloud = P.DeviceCloud(torch.from_numpy(p).to(DEV), torch.tensor([n], dtype=torch.int32, device=DEV))
+    assert cloud.bound == bound
+    picked = P.select_device(cloud, flags=torch.from_numpy(flags).to(DEV))
+    want = p[:n][flags[:n] != 0]
+    assert len(want) == {"half": len(want), "none": 0, "all": n}[fill]
+    assert torch.equal(picked.count.cpu(), torch.tensor([len(want)], dtype=torch.int32))
+    assert torch.equal(picked.pts[:len(want)].cpu(), torch.from_numpy(want))
+
+
+@gpu
 def test_tabletop_end_to_end_device():
     s = synth.tabletop_scene(2, 48, 64, seed=1, band=0.12)
     args = (s["depth"], s["R"], s["t"], s["intr"], s["bbox"])
