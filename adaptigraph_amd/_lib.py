@@ -142,6 +142,10 @@ SIGNATURES = {
     "ag_segment_sum": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_void_p]),
     "ag_message_forward": (c_int, [c_void_p] * 6 + [c_int64, c_int, c_void_p]),
     "ag_message_backward": (c_int, [c_void_p] * 8 + [c_int64, c_int, c_void_p]),
+    "ag_edge_views_workspace_bytes": (c_size_t, [c_int] * 2),
+    "ag_edge_views": (c_int, [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 4),
+    "ag_step_update_forward": (c_int, [c_void_p] * 6 + [c_int] * 6 + [c_float] + [c_void_p] * 3),
+    "ag_step_update_backward": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_void_p] * 7),
     # training path: dense stacks
     "ag_train_pack": (c_int, [c_void_p] * 2 + [c_int] * 8 + [c_void_p] * 2),
     "ag_train_chain": (c_int, [c_int] * 3 + [c_void_p] * 2 + [P(c_void_p), c_void_p, P(c_void_p), c_void_p, c_int64, c_int, c_void_p]),

@@ -564,6 +564,21 @@ void ag_launch_chain(int kind, int backward, int b3, const AgChainArgsPOD &p, in
 void ag_launch_edge_inputs_fwd(const float *tab, int D, int A, int G, const int *recv, const int *send, float *out, long long E, hipStream_t s);
 void ag_launch_edge_inputs_bwd(const float *tab, int D, int A, int G, const int *recv, const int *send, const int *row_ptr, const int *col_ptr,
                                const int *perm, const float *gout, float *g_r, float *g_s, float *gtab, long long E, long long M, hipStream_t s);
+// ag_train.hip: the sender-side view of an edge list (counting sort per sample); counters of a sample with N > AG_VIEWS_LDS_N live in `counters` (B * N words)
+#define AG_VIEWS_LDS_N 8192
+void ag_launch_edge_views(const int32_t *row_ptr, const int32_t *send, int B, int N, int32_t *col_ptr, int32_t *perm, int32_t *counters, hipStream_t s);
+// ag_step_update.hip: a model step's state update of the differentiable rollouts, out of place, and its adjoint
+struct AgStepUpdateArgs {
+    const float *pred, *state, *delta, *rec;      // forward inputs (backward reads pred only)
+    const int32_t *repeat;
+    const uint8_t *obj_mask;
+    int B, H, N, n_p, step, height_mode;
+    float raise;
+    float *state_out, *rec_out;                   // forward outputs
+    const float *g_state_out, *g_rec_out;         // backward inputs
+    float *g_pred, *g_state, *g_delta, *g_rec;    // backward outputs
+};
+void ag_launch_step_update(const AgStepUpdateArgs &a, int backward, hipStream_t s);
 void ag_launch_add3_relu(const float *a, const float *b, const float *c, float *y, long long n, hipStream_t s);
 void ag_launch_relu_mask(const float *g, const float *y, float *out, long long n, hipStream_t s);
 size_t ag_weight_grads_ws_floats(long long rows, int n_layers);

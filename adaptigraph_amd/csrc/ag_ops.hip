@@ -349,6 +349,60 @@ int ag_message_backward(const float *eterm, const float *hr, const float *hs, co
     return AG_OK;
 }
 
+size_t ag_edge_views_workspace_bytes(int B, int N)
+{
+    return (B > 0 && N > AG_VIEWS_LDS_N) ? (size_t)B * N * sizeof(int32_t) : 0;
+}
+
+int ag_edge_views(const int32_t *row_ptr, const int32_t *edge_send, int B, int N, int32_t *col_ptr, int32_t *send_perm, void *workspace,
+                  ag_stream_t stream)
+{
+    if (B < 1 || N < 1 || (long long)B * N >= 0x7fffffffLL) return ag_fail(AG_ERR_ARG, "ag_edge_views: bad sizes B=%d N=%d", B, N);
+    if (!row_ptr || !edge_send || !col_ptr || !send_perm) return ag_fail(AG_ERR_ARG, "ag_edge_views: null argument");
+    if (N > AG_VIEWS_LDS_N && !workspace) return ag_fail(AG_ERR_WS, "ag_edge_views: N=%d needs a workspace of %zu bytes", N, ag_edge_views_workspace_bytes(B, N));
+    ag_launch_edge_views(row_ptr, edge_send, B, N, col_ptr, send_perm, static_cast<int32_t *>(workspace), static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+static int step_update_check(const char *what, int B, int H, int N, int n_p, int height_mode, const void *obj_mask)
+{
+    if (B < 1 || H < 1 || n_p < 1 || N < n_p || (long long)B * H * N * 3 >= 0x7fffffffLL)
+        return ag_fail(AG_ERR_ARG, "%s: bad sizes B=%d H=%d N=%d n_p=%d", what, B, H, N, n_p);
+    if (height_mode != AG_HEIGHT_MIN && height_mode != AG_HEIGHT_MASKED_MEAN) return ag_fail(AG_ERR_ARG, "%s: height_mode=%d", what, height_mode);
+    if (height_mode == AG_HEIGHT_MASKED_MEAN && !obj_mask) return ag_fail(AG_ERR_ARG, "%s: AG_HEIGHT_MASKED_MEAN needs obj_mask", what);
+    return AG_OK;
+}
+
+int ag_step_update_forward(const float *pred, const float *state, const float *delta, const float *rec, const int32_t *repeat, const uint8_t *obj_mask,
+                           int B, int H, int N, int n_p, int step, int height_mode, float raise, float *state_out, float *rec_out, ag_stream_t stream)
+{
+    if (const int rc = step_update_check("ag_step_update_forward", B, H, N, n_p, height_mode, obj_mask)) return rc;
+    if (!pred || !state || !delta || !repeat || !state_out || !rec_out) return ag_fail(AG_ERR_ARG, "ag_step_update_forward: null argument");
+    AgStepUpdateArgs a{};
+    a.pred = pred; a.state = state; a.delta = delta; a.rec = rec; a.repeat = repeat; a.obj_mask = obj_mask;
+    a.B = B; a.H = H; a.N = N; a.n_p = n_p; a.step = step; a.height_mode = height_mode; a.raise = raise;
+    a.state_out = state_out; a.rec_out = rec_out;
+    ag_launch_step_update(a, 0, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
+int ag_step_update_backward(const float *pred, const int32_t *repeat, const uint8_t *obj_mask, int B, int H, int N, int n_p, int step, int height_mode,
+                            const float *grad_state_out, const float *grad_rec_out, float *grad_pred, float *grad_state, float *grad_delta,
+                            float *grad_rec, ag_stream_t stream)
+{
+    if (const int rc = step_update_check("ag_step_update_backward", B, H, N, n_p, height_mode, obj_mask)) return rc;
+    if (!pred || !repeat || !grad_state_out || !grad_pred || !grad_state || !grad_delta) return ag_fail(AG_ERR_ARG, "ag_step_update_backward: null argument");
+    AgStepUpdateArgs a{};
+    a.pred = pred; a.repeat = repeat; a.obj_mask = obj_mask;
+    a.B = B; a.H = H; a.N = N; a.n_p = n_p; a.step = step; a.height_mode = height_mode;
+    a.g_state_out = grad_state_out; a.g_rec_out = grad_rec_out; a.g_pred = grad_pred; a.g_state = grad_state; a.g_delta = grad_delta; a.g_rec = grad_rec;
+    ag_launch_step_update(a, 1, static_cast<hipStream_t>(stream));
+    AG_HIP(hipGetLastError());
+    return AG_OK;
+}
+
 int ag_train_pack(const float *W, const float *bias, int n_out, int n_in, int ld, int col0, int transposed, int compact, int n_tiles,
                   int precision, float *dst, ag_stream_t stream)
 {

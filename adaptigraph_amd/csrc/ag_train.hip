@@ -7,6 +7,7 @@
 // w.r.t. gathered rows are segment sums over a (pointer, permutation) view of the same edges, so every reduction has
 // a fixed order — no atomics, bit-reproducible gradients.  Feature width D is arbitrary (plain row-major torch tensors):
 // one thread per (row, feature), consecutive threads on consecutive features, so every access is coalesced along D.
+#include "ag_block_dev.h"
 #include "ag_common.h"
 
 namespace {
@@ -258,6 +259,68 @@ __global__ __launch_bounds__(256) void relu_mask_kernel(const float4 *g, const f
     out[t] = make_float4(v.x > 0.f ? u.x : 0.f, v.y > 0.f ? u.y : 0.f, v.z > 0.f ? u.z : 0.f, v.w > 0.f ? u.w : 0.f);
 }
 
+// ---- the sender-side view of a receiver-sorted edge list (ag_edge_views) ----------------------------------------------------
+// perm = the edges in ascending sender order, equal senders in edge order; col_ptr = the prefix of the per-sender counts: what the adjoint of a
+// gather by sender reads (segment_sum_kernel above).  The senders of sample b lie in [bN, (b+1)N) and its edges are [row_ptr[bN], row_ptr[(b+1)N)),
+// so the sort is one counting sort per sample, one workgroup each, and col_ptr[bN + i] = row_ptr[bN] + (edges of the sample with a smaller sender):
+// no scan across workgroups.  Three passes over the sample's edges and senders:
+//   count   — integer atomics into the sample's N counters (LDS; `counters` for a sample beyond AG_VIEWS_LDS_N); the counters are zeroed here
+//   scan    — 256 senders at a time (block_exclusive_scan), leaving each sender's first slot in its counter
+//   scatter — 256 edges at a time IN EDGE ORDER: a lane's rank among the lanes of its wave with the same sender comes from one ballot per bit
+//             of the sender index, the four waves take their turn in order, and the first lane of a group moves the sender's counter on.
+// A slot is therefore a function of the edge list alone: no atomic assigns one.
+template <bool LDS>
+__global__ __launch_bounds__(256) void edge_views_kernel(const int32_t *row_ptr, const int32_t *send, int B, int N, int32_t *col_ptr, int32_t *perm,
+                                                         int32_t *counters)
+{
+    __shared__ int32_t lds_cnt[LDS ? AG_VIEWS_LDS_N : 1];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long n0 = (long long)b * N;
+    int32_t *cnt = counters + n0;                                        // (read only where the counters are not in LDS)
+    auto slot = [&](int i) -> int32_t & { if constexpr (LDS) return lds_cnt[i]; else return cnt[i]; };
+    const int e0 = row_ptr[n0], e1 = row_ptr[n0 + N];
+    for (int i = tid; i < N; i += 256) slot(i) = 0;
+    __syncthreads();
+    for (int e = e0 + tid; e < e1; e += 256) {
+        const long long k = (long long)send[e] - n0;
+        if (k >= 0 && k < N) atomicAdd(&slot((int)k), 1);
+    }
+    __syncthreads();
+    int base = 0;
+    for (int i0 = 0; i0 < N; i0 += 256) {
+        const int i = i0 + tid;
+        const int v = i < N ? slot(i) : 0;
+        int total;
+        const int first = base + block_exclusive_scan(v, &total);      // (two barriers: every thread of the workgroup gets here)
+        if (i < N) { slot(i) = first; col_ptr[n0 + i] = e0 + first; }
+        base += total;
+    }
+    if (b == B - 1 && tid == 0) col_ptr[n0 + N] = e1;
+    __syncthreads();
+    const int n_bits = 32 - __clz(N - 1 > 0 ? N - 1 : 0);              // bits that tell the sender indices 0 .. N-1 apart
+    for (int c0 = e0; c0 < e1; c0 += 256) {
+        const int e = c0 + tid;
+        const long long k = e < e1 ? (long long)send[e] - n0 : -1;
+        const bool valid = k >= 0 && k < N;
+        const int key = valid ? (int)k : 0;
+        unsigned long long same = __ballot(valid);                       // -> the valid lanes of this wave with this lane's sender
+        for (int bit = 0; bit < n_bits; ++bit) {
+            const bool on = (key >> bit) & 1;
+            const unsigned long long set = __ballot(on);
+            same &= on ? set : ~set;
+        }
+        const int rank = ballot_rank(same, lane), n_same = __popcll(same);
+        for (int w = 0; w < 4; ++w) {
+            if (wave == w && valid) {
+                const int at = slot(key);                                // every lane of the group reads the counter before its first lane moves it:
+                perm[e0 + at + rank] = e;                                // the store below needs the loaded value, and a wave's loads return together
+                if (rank == 0) slot(key) = at + n_same;
+            }
+            __syncthreads();
+        }
+    }
+}
+
 inline unsigned blocks_for(long long total) { return (unsigned)((total + 255) / 256); }
 
 }  // namespace
@@ -332,4 +395,11 @@ void ag_launch_edge_inputs_bwd(const float *tab, int D, int A, int G, const int 
 {
     if (E > 0) hipLaunchKernelGGL(edge_inputs_bwd_kernel, dim3(blocks_for(E)), dim3(256), 0, s, tab, D, A, G, recv, send, gout, g_r, g_s, E);
     if (M > 0) hipLaunchKernelGGL(edge_inputs_reduce_kernel, dim3(blocks_for(M * D)), dim3(256), 0, s, g_r, g_s, row_ptr, col_ptr, perm, gtab, M * D, D);
+}
+
+void ag_launch_edge_views(const int32_t *row_ptr, const int32_t *send, int B, int N, int32_t *col_ptr, int32_t *perm, int32_t *counters, hipStream_t s)
+{
+    if (B < 1 || N < 1) return;
+    if (N <= AG_VIEWS_LDS_N) hipLaunchKernelGGL(edge_views_kernel<true>, dim3(B), dim3(256), 0, s, row_ptr, send, B, N, col_ptr, perm, counters);
+    else hipLaunchKernelGGL(edge_views_kernel<false>, dim3(B), dim3(256), 0, s, row_ptr, send, B, N, col_ptr, perm, counters);
 }

@@ -2,7 +2,8 @@
 
 `dynamics(state, action, model, device, ppm_optimizer, physics_param=None)` (:11-205) and
 `dynamics_masked(state_init, state_mask, action, model, device, ppm_optimizer, physics_param=None)` (:208-399)
-keep the reference signatures and return dicts; `dynamics_differentiable` is `dynamics` under autograd (gradient planning).  The per-sample set-up (tool key-points from the decoded
+keep the reference signatures and return dicts; `dynamics_differentiable` is `dynamics` under autograd (gradient planning) and
+`dynamics_masked_differentiable` is `dynamics_masked` under autograd (sys-id by gradient).  The per-sample set-up (tool key-points from the decoded
 action) is a handful of tiny device tensor ops; the inner loop — edges -> GNN forward -> record-on-repeat ->
 tool advance -> history shift -> edge rebuild — is one `ag_rollout` call with no host synchronisation
 (the reference syncs three times per step: truncate_graph, n_rels.max().item(), pad_torch).
@@ -381,7 +382,108 @@ def _frozen_view(model):
               non_rigid_predictor=NS(linear_0=lin(d.linear_0), linear_1=lin(d.linear_1), linear_2=lin(d.linear_2)))
 
 
-def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics_param=None):
+_LANES = {}
+
+
+def block_sum(x):
+    """x (B, n) -> (B,): the sum over n in the ORDER of the rollout kernels' workgroup reduction (rollout_step_kernel, ag_step_update): 256
+    strided per-thread partials, the xor butterfly 32, 16, .. 1 inside each of the four waves, then (w0 + w1) + (w2 + w3) — as tensor ops, so that
+    the masked mean of the tensor-op step update has the kernels' bits.  Differentiable."""
+    B, n = x.shape
+    k = max(1, -(-n // 256))
+    x = torch.nn.functional.pad(x, (0, k * 256 - n)).view(B, k, 256)
+    acc = torch.zeros((B, 256), dtype=x.dtype, device=x.device)
+    for j in range(k):
+        acc = acc + x[:, j]
+    v = acc.view(B, 4, 64)
+    lanes = _LANES.get(str(x.device))
+    if lanes is None:
+        lanes = _LANES[str(x.device)] = torch.arange(64, device=x.device)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[..., lanes ^ o]
+    w = v[..., 0]
+    return (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+
+
+def step_update_ops(pred, states, delta, rec, repeat, ai, height_mode=_lib.AG_HEIGHT_MIN, obj_mask=None, raise_by=0.0):
+    """The tail of a model step as tensor ops (forward_dynamics.py:160-176 / :356-372): record where repeat == ai, the tool rows advanced by
+    delta at the height of the prediction (min y, or the masked mean of y in the kernels' summation order) plus the raise, the history shifted
+    -> (states, rec).  `dynamics_differentiable` runs this form; `step_update` is the same function in one launch each way."""
+    bsz, n_obj = pred.shape[0], pred.shape[1]
+    n_t = states.shape[2] - n_obj
+    rec = torch.where((repeat == ai)[:, None, None], pred, rec)
+    tool = states[:, -1, n_obj:] + delta[:, n_obj:]
+    if height_mode == _lib.AG_HEIGHT_MIN:
+        y = pred[:, :, 1].min(dim=1).values
+    else:
+        w = obj_mask.to(pred.dtype)
+        y = block_sum(pred[:, :, 1] * w) / block_sum(w)
+    y_cur = y + raise_by
+    tool = torch.stack([tool[..., 0], y_cur[:, None].expand(bsz, n_t), tool[..., 2]], dim=-1)
+    states = torch.cat([states[:, 1:], torch.cat([pred, tool], dim=1)[:, None]], dim=1)
+    return states, rec
+
+
+class _StepUpdate(torch.autograd.Function):
+    """step_update_ops in one launch (ag_step_update_forward) with its adjoint in one (ag_step_update_backward): the prediction has ONE consumer,
+    and the three contributions to its gradient (newest frame, record, tool height) meet in the kernel's fixed order."""
+
+    @staticmethod
+    def forward(ctx, pred, states, delta, rec, repeat, ai, height_mode, obj_u8, raise_by):
+        _lib._require_gpu(pred, "pred")
+        pred, states, delta, rec = (t.contiguous().float() for t in (pred, states, delta, rec))
+        B, H, N, _ = states.shape
+        n_p = pred.shape[1]
+        assert pred.shape == (B, n_p, 3) and delta.shape == (B, N, 3) and rec.shape == pred.shape and repeat.dtype == torch.int32
+        states_out, rec_out = torch.empty_like(states), torch.empty_like(pred)
+        _lib.call("ag_step_update_forward", pred.device, pred, states, delta, rec, repeat, obj_u8, B, H, N, n_p, int(ai), int(height_mode),
+                  float(raise_by), states_out, rec_out)
+        ctx.save_for_backward(pred, repeat, obj_u8)
+        ctx.meta = (B, H, N, n_p, int(ai), int(height_mode))
+        return states_out, rec_out
+
+    @staticmethod
+    def backward(ctx, g_states, g_rec):
+        pred, repeat, obj_u8 = ctx.saved_tensors
+        B, H, N, n_p, ai, mode = ctx.meta
+        g_states, g_rec = g_states.contiguous().float(), g_rec.contiguous().float()
+        g_pred, g_rec_in = torch.empty_like(pred), torch.empty_like(pred)
+        g_in = torch.empty_like(g_states)
+        g_delta = torch.empty((B, N, 3), dtype=torch.float32, device=pred.device)
+        _lib.call("ag_step_update_backward", pred.device, pred, repeat, obj_u8, B, H, N, n_p, ai, mode, g_states, g_rec, g_pred, g_in, g_delta, g_rec_in)
+        return g_pred, g_in, g_delta, g_rec_in, None, None, None, None, None
+
+
+def step_update(pred, states, delta, rec, repeat, ai, height_mode=_lib.AG_HEIGHT_MIN, obj_mask=None, raise_by=0.0):
+    """step_update_ops on the device kernels, under autograd: pred (B,n_p,3), states (B,H,N,3), delta (B,N,3), rec (B,n_p,3), repeat (B,) int32,
+    obj_mask (B,n_p) bool for AG_HEIGHT_MASKED_MEAN -> (states, rec)."""
+    obj_u8 = _u8(obj_mask, pred.device) if obj_mask is not None else None
+    return _StepUpdate.apply(pred, states, delta, rec, repeat, ai, height_mode, obj_u8, raise_by)
+
+
+def _model_step(view, phys_key, consts, edges, repeat, ai, height, states, delta, phys, rec):
+    """One model step of the differentiable rollouts, shared by both drivers: the training forward on the step's edge lists, then the state update.
+    consts = (attrs, p_instance); edges = (csr, EdgeViews); height = (mode, obj_mask, raise_by, kernel) — kernel: step_update, else step_update_ops.
+    A function of the four trailing tensors alone: under checkpoint_steps only they are kept, and this runs again in the backward pass."""
+    from .train_model import TrainableDynamicsPredictor
+    attrs, p_instance = consts
+    csr, views = edges
+    mode, obj_mask, raise_by, kernel = height
+    pred, _ = TrainableDynamicsPredictor.forward(view, states, attrs, csr, None, p_instance, action=delta, edge_views=views, **{phys_key: phys})
+    return (step_update if kernel else step_update_ops)(pred, states, delta, rec, repeat, ai, mode, obj_mask, raise_by)
+
+
+def _run_step(checkpoint_steps, *args):
+    """_model_step, or — checkpoint_steps — the same graph whose saved activations are dropped and recomputed from the step's inputs when the
+    backward pass first asks for one.  The autograd graph is the same either way and every kernel is deterministic, so gradients keep their bits."""
+    if not checkpoint_steps:
+        return _model_step(*args)
+    from functools import partial
+    from torch.utils.checkpoint import checkpoint
+    return checkpoint(partial(_model_step, *args[:-4]), *args[-4:], use_reentrant=False, preserve_rng_state=False)
+
+
+def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics_param=None, checkpoint_steps=False):
     """`dynamics` under autograd: the same signature, output dict and semantics (forward_dynamics.py:12-205 without @torch.no_grad,
     including the .detach() of the object state between look-ahead pushes, the tool height from min y, the per-sample action_repeat
     record and gripper_enable), with gradients to `action` (x, z, theta; the push length only counts steps) and to physics_param
@@ -391,9 +493,14 @@ def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics
     TrainableDynamicsPredictor.forward (HIP gather / segment-sum kernels and fused MFMA chains, forward and backward).
     Cost: one host read per model step (the edge count of EdgeViews) plus one per look-ahead push (its step count), and memory of
     O(steps x saved activations): meant for planning batches of tens to a few hundred samples, not the 20 000 of an MPPI sweep,
-    which `dynamics` serves without autograd."""
+    which `dynamics` serves without autograd.
+
+    checkpoint_steps: each model step keeps only its inputs (history frames, tool delta, physics, the step's edge lists) and is recomputed
+    in the backward pass: memory O(steps x inputs) + one step's activations, the same outputs and gradients bit for bit.  The state update is
+    then ag_step_update's one launch each way instead of the tensor ops (step_update_ops), whose values and gradients it reproduces bit for
+    bit (tests/test_sysid_grad.py) — except where two particles share the minimum height exactly: the kernel sends the height's gradient to
+    the first of them, torch.min to the one it returned."""
     from .graph import build_edges
-    from .train_model import TrainableDynamicsPredictor
     from .train_ops import EdgeViews
 
     task = ppm_optimizer.task_config
@@ -410,6 +517,7 @@ def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics
     raise_by = 0.01 * ratio if task["gripper_enable"] else 0.0
     obj_still = torch.zeros((bsz, n_obj, 3), device=device)
     max_steps = repeat.max(dim=0).values.tolist()
+    rep_cols = repeat.t().contiguous()      # (n_look, B) int32: a look-ahead step's column contiguous, as ag_step_update reads it
     seqs = []
     obj = state[None].expand(bsz, n_obj, 3)
     for li in range(n_look):
@@ -424,15 +532,63 @@ def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics
             with torch.no_grad():
                 csr = build_edges(states[:, -1].detach(), ppm_optimizer.adj_thresh, mask, tool_mask, task["topk"], task["connect_tools_all"],
                                   "batch", max_tools=n_t)
-            pred, _ = TrainableDynamicsPredictor.forward(view, states, attrs, csr, None, p_instance, action=delta, edge_views=EdgeViews(csr),
-                                                         **{phys_key: phys})
-            rec = torch.where((repeat[:, li] == ai)[:, None, None], pred, rec)
-            tool = states[:, -1, n_obj:] + delta[:, n_obj:]
-            y_cur = pred[:, :, 1].min(dim=1).values + raise_by
-            tool = torch.stack([tool[..., 0], y_cur[:, None].expand(bsz, n_t), tool[..., 2]], dim=-1)
-            states = torch.cat([states[:, 1:], torch.cat([pred, tool], dim=1)[:, None]], dim=1)
+            states, rec = _run_step(checkpoint_steps, view, phys_key, (attrs, p_instance), (csr, EdgeViews(csr)), rep_cols[li], ai,
+                                    (_lib.AG_HEIGHT_MIN, None, raise_by, bool(checkpoint_steps)), states, delta, phys, rec)
         seqs.append(rec)
     return {"state_seqs": torch.stack(seqs, dim=1), "action_seqs": decoded}
+
+
+def dynamics_masked_differentiable(state_init, state_mask, action, model, device, ppm_optimizer, physics_param=None, checkpoint_steps=False):
+    """`dynamics_masked` under autograd — the objective of sys-id by gradient: the same signature, output dict and semantics
+    (forward_dynamics.py:208-399 without @torch.no_grad: per-sample start clouds with masks, one push, the tool height from the masked mean
+    of y at the start and at every step, the per-sample action_repeat record, gripper_enable, a per-sample physics_param of shape (bsz, d)),
+    with gradients to physics_param tensors that require grad, to the masked-in rows of state_init and to x, z, theta of `action`.  Model
+    weights are used detached.
+
+    Per model step: the HIP edge builder under no_grad, both views of its edge list on the device (EdgeViews(device_views=True): one launch
+    of ag_edge_views), TrainableDynamicsPredictor.forward, and the state update in one launch each way (ag_step_update_forward / _backward).
+    One host read per model step (the edge count) plus one for the step count.  checkpoint_steps: as in `dynamics_differentiable`."""
+    from .graph import build_edges
+    from .train_ops import EdgeViews
+
+    task = ppm_optimizer.task_config
+    n_his, push_length = task["n_his"], task["push_length"]
+    state_mask = state_mask.to(device)
+    obj_mask = state_mask.bool()
+    state = state_init.to(device, torch.float32)
+    state = torch.where(obj_mask[:, :, None], state, state.detach())      # masked-out rows carry their values along, never a gradient
+    action = action.to(device, torch.float32)
+    bsz, n_obj = state.shape[0], state.shape[1]
+    decoded, repeat = decode_action(action[:, None], push_length=push_length)
+    decoded, repeat = decoded[:, 0], repeat[:, 0].contiguous()
+    n_t = ppm_optimizer.eef_num
+    N = n_obj + n_t
+
+    cnt = state_mask.sum(dim=1)
+    y = (state[:, :, 1] * state_mask).sum(dim=1) / cnt                            # forward_dynamics.py:235
+    eef, dlt, raise_by = _place_tool(task, decoded, action[:, 2], y, device)
+    states = torch.cat([state[:, None].expand(bsz, n_his, n_obj, 3), eef[:, None].expand(bsz, n_his, n_t, 3)], dim=2)
+    delta = torch.cat([torch.zeros((bsz, n_obj, 3), device=device), dlt], dim=1)
+    attrs = torch.zeros((bsz, N, 2), device=device)
+    attrs[:, :n_obj, 0] = state_mask.float()
+    attrs[:, n_obj:, 1] = 1.0
+    p_instance = torch.zeros((bsz, n_obj, task["max_n"]), device=device)           # first `count` slots, :292-300
+    p_instance[:, :, 0] = (torch.arange(n_obj, device=device)[None] < cnt[:, None]).float()
+    mask = torch.ones((bsz, N), dtype=torch.bool, device=device)
+    mask[:, :n_obj] = obj_mask
+    tool_mask = torch.zeros((bsz, N), dtype=torch.bool, device=device)
+    tool_mask[:, n_obj:] = True
+    phys = _physics(ppm_optimizer, physics_param, bsz, device)
+    phys_key = ppm_optimizer.material + "_physics_param"
+    view = _frozen_view(model)
+    rec = torch.zeros((bsz, n_obj, 3), device=device)
+    for ai in range(1, 1 + int(repeat.max().item())):
+        with torch.no_grad():
+            csr = build_edges(states[:, -1].detach(), ppm_optimizer.adj_thresh, mask, tool_mask, task["topk"], task["connect_tools_all"],
+                              "batch", max_tools=n_t)
+        states, rec = _run_step(checkpoint_steps, view, phys_key, (attrs, p_instance), (csr, EdgeViews(csr, device_views=True)), repeat, ai,
+                                (_lib.AG_HEIGHT_MASKED_MEAN, obj_mask, raise_by, True), states, delta, phys, rec)
+    return {"state_seqs": rec, "action_seqs": decoded}
 
 
 @torch.no_grad()

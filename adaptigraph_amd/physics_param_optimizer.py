@@ -10,6 +10,9 @@ this engine anyway: graphs in a batch are independent, so ALL candidates of a se
 of `candidates x interactions` graphs (`dynamics_error_batch`).  `optimize` therefore does a dense batched sweep of
 [-0.2, 1.2] followed by batched zoom refinements (1-D), or a batched cross-entropy search (>1-D): same objective, same
 bounds, same outputs, different (derivative-free) search.
+
+`optimize(..., method="gd")` searches by gradient instead: the objective is differentiable end to end (`dynamics_masked_differentiable`, the
+masked chamfer's HIP backward), and one gradient step costs one forward and one backward however many parameters there are.
 """
 import copy
 import glob
@@ -18,7 +21,7 @@ import os
 import numpy as np
 import torch
 
-from .forward_dynamics import dynamics_masked
+from .forward_dynamics import dynamics_masked, dynamics_masked_differentiable
 from .losses import mean_chamfer_device
 
 PARAM_LO, PARAM_HI = -0.2, 1.2      # gp_minimize bounds / CMA bounds of the reference (:99, :151)
@@ -75,11 +78,76 @@ def dynamics_error(physics_param, ppm_optimizer, state_init_list, state_real_lis
     return float(err.double().mean().item())
 
 
+METHODS = ("sweep", "gd")
+GD_LR = (0.1, 1e-4)         # Adam's step size at the first and the last iteration, geometric in between.  The objective is a mean of DISTANCES: V-shaped at
+                            # its minimum, where a gradient keeps its length however close the parameter is, so only a shrinking step settles; and Adam
+                            # moves a coordinate by about the step size whatever the gradient's length, so the steps must add up to the way from the
+                            # first generation's best point to the minimum: 0.1 / (1 - 0.001^(1/29)) = 0.47 of the 1.4-wide box at 30 iterations
+                            # (a first step of 0.03 adds up to 0.14 there: on the two-parameter task of bench_sysid.py every start stalled short)
+GD_BETAS = (0.5, 0.9)       # short memories: across the V the gradient changes sign from one step to the next
+
+
+def _first_generation(dims, iterations, init_param, seed):
+    """The candidates of the sweep's first generation: the grid over the box (1-D), the seeded normal cloud around the current parameter (> 1-D)."""
+    if dims == 1:
+        return np.linspace(PARAM_LO, PARAM_HI, max(5, iterations // 3), dtype=np.float64)[:, None]
+    rng = np.random.default_rng(seed)
+    return np.clip(init_param.astype(np.float64) + 0.2 * rng.standard_normal((max(8, iterations // 5), dims)), PARAM_LO, PARAM_HI)
+
+
+def _optimize_gd(ppm_optimizer, ev, dims, init_param, iterations, n_starts, seed, state_init_list, state_real_list, actions, checkpoint_steps):
+    """Identification by gradient: the best `1 + n_starts` candidates of one batched sweep generation, improved TOGETHER by Adam — each iteration is
+    one forward and one backward of `starts x interactions` graphs through dynamics_masked_differentiable and the differentiable masked chamfer,
+    whatever the number of parameters — clamped to the box after every step; one host read per iteration (the points and their objective).
+    The last point and the best-scoring point of every start are then scored by the sweep's own objective (dynamics_error_batch), so that the
+    choice among them does not depend on the differentiable path's arithmetic.  -> (x_iters, func_vals, scored) of every evaluated point;
+    scored: the point's value is the sweep's objective (not the differentiable path's)."""
+    device = ppm_optimizer.device
+    material = ppm_optimizer.material
+    xs = _first_generation(dims, iterations, init_param, seed)
+    fs = ev(xs)
+    history_x, history_f = [xs], [fs]
+    starts = xs[np.argsort(fs, kind="stable")[: 1 + max(0, int(n_starts))]]
+    S, n = starts.shape[0], len(actions)
+    init, init_mask, real, real_mask, act = _pad_interactions(ppm_optimizer, state_init_list, state_real_list, actions)
+    rep = lambda x: x[None].expand((S,) + tuple(x.shape)).reshape((S * n,) + tuple(x.shape[1:]))
+    init_r, imask_r, real_r, rmask_r, act_r = rep(init), rep(init_mask), rep(real), rep(real_mask), rep(act)
+    P = torch.tensor(starts, dtype=torch.float32, device=device, requires_grad=True)
+    opt = torch.optim.Adam([P], lr=GD_LR[0], betas=GD_BETAS)
+    T = int(iterations)
+    for t in range(T):
+        opt.param_groups[0]["lr"] = GD_LR[0] * (GD_LR[1] / GD_LR[0]) ** (t / max(T - 1, 1))
+        opt.zero_grad(set_to_none=True)
+        out = dynamics_masked_differentiable(init_r, imask_r, act_r, ppm_optimizer.model, device, ppm_optimizer,
+                                             physics_param={material: P[:, None, :].expand(S, n, dims).reshape(S * n, dims)},
+                                             checkpoint_steps=checkpoint_steps)
+        err = mean_chamfer_device(out["state_seqs"], real_r, imask_r, rmask_r).reshape(S, n).double().mean(dim=1)
+        err.sum().backward()
+        host = torch.cat([P.detach().double().reshape(-1), err.detach()]).cpu().numpy()      # the iteration's one host read
+        history_x.append(host[: S * dims].reshape(S, dims)); history_f.append(host[S * dims:])
+        opt.step()
+        with torch.no_grad():
+            P.clamp_(PARAM_LO, PARAM_HI)
+    gx, gf = np.concatenate(history_x[1:]).reshape(T, S, dims), np.concatenate(history_f[1:]).reshape(T, S)
+    best_seen = gx[np.nanargmin(np.where(np.isfinite(gf), gf, np.inf), axis=0), np.arange(S)]
+    final = np.concatenate([P.detach().double().cpu().numpy(), best_seen])
+    history_x.append(final); history_f.append(ev(final))
+    scored = np.concatenate([np.ones(len(xs), bool), np.zeros(T * S, bool), np.ones(len(final), bool)])
+    return np.concatenate(history_x), np.concatenate(history_f), scored
+
+
 def optimize(ppm_optimizer, actions, state_init_list, state_pred_list, state_real_list, num_optim_trials=1, iter_idx=0,
-             iterations=50, return_res=False, seed=42):
+             iterations=50, return_res=False, seed=42, method="sweep", n_starts=3, checkpoint_steps=False):
     """Same contract as the reference's `optimize` / `optimize_cma` (:75-175): -> (ppm, error, init_error[, res]).
     `iterations` bounds the number of objective evaluations PER INTERACTION SET exactly as n_calls does there; they are
-    spent in batched generations."""
+    spent in batched generations.
+    method: "sweep" — the derivative-free batched search; "gd" — gradient descent from the sweep's first generation (`_optimize_gd`), where
+    `iterations` bounds the gradient steps and `n_starts` further starts run beside the generation's best (checkpoint_steps: see
+    forward_dynamics.dynamics_masked_differentiable)."""
+    if method not in METHODS:
+        raise ValueError(f"optimize: method={method!r}, expected one of {METHODS}")
+    if int(n_starts) < 0:
+        raise ValueError(f"optimize: n_starts={n_starts} (>= 0)")
     dims = sum(ppm_optimizer.material_dims.values())
     material = ppm_optimizer.material
     init_param = ppm_optimizer.physics_param[material].detach().float().cpu().numpy().reshape(-1)
@@ -89,8 +157,12 @@ def optimize(ppm_optimizer, actions, state_init_list, state_pred_list, state_rea
         return init_error
     if iterations < 0:
         iterations = 200
-    history_x, history_f = [], []
-    if dims == 1:
+    history_x, history_f, scored = [], [], None
+    if method == "gd":
+        X, F, scored = _optimize_gd(ppm_optimizer, ev, dims, init_param, iterations, n_starts, seed, state_init_list, state_real_list, actions,
+                            checkpoint_steps)
+        history_x, history_f = [X], [F]
+    elif dims == 1:
         per_gen = max(5, iterations // 3)
         lo, hi = PARAM_LO, PARAM_HI
         for _ in range(3):                                   # sweep, then zoom twice around the incumbent
@@ -111,7 +183,7 @@ def optimize(ppm_optimizer, actions, state_init_list, state_pred_list, state_rea
             elite = xs[np.argsort(fs)[: max(2, pop // 4)]]
             mean, std = elite.mean(0), elite.std(0) + 1e-3
     X, F = np.concatenate(history_x), np.concatenate(history_f)
-    best = X[int(np.argmin(F))].astype(np.float32)
+    best = X[int(np.argmin(F if scored is None else np.where(scored, F, np.inf)))].astype(np.float32)
     error = dynamics_error(best.tolist(), ppm_optimizer, state_init_list, state_real_list, actions)
     res = {"x_iters": X, "func_vals": F, "x": best, "fun": error}
     return (best, error, init_error, res) if return_res else (best, error, init_error)
@@ -123,7 +195,10 @@ optimize_cma = optimize      # one batched search covers both of the reference's
 class PhysicsParamOnlineOptimizer:
     """Same attributes and file contract as the reference class (:18-72)."""
 
-    def __init__(self, task_config, model, material, device, save_dir):
+    def __init__(self, task_config, model, material, device, save_dir, method="sweep"):
+        if method not in METHODS:
+            raise ValueError(f"PhysicsParamOnlineOptimizer: method={method!r}, expected one of {METHODS}")
+        self.method = method
         self.task_config = task_config
         self.model = model
         self.material = material
@@ -147,7 +222,7 @@ class PhysicsParamOnlineOptimizer:
             state_pred.append(res["state_pred"]); state_real.append(res["state_real"])
         assert iterations > 0
         ppm, error, error_init, _ = optimize(self, act, state_init, state_pred, state_real, iter_idx=i, iterations=iterations,
-                                             return_res=True)
+                                             return_res=True, method=self.method)
         self.physics_param[self.material] = torch.tensor(ppm, dtype=torch.float32, device=self.device).clamp(-0.2, 1.2)
         np.savez(os.path.join(self.save_dir, f"ppo_{i}.npz"), physics_param=np.array(ppm), error=error, error_init=error_init)
         return ppm, error, error_init

@@ -17,14 +17,28 @@ from .graph import CSREdges
 
 class EdgeViews:
     """Receiver- and sender-sorted views of one batch's edges.  One host read (the edge count) per batch; the reference
-    training loop keeps the edges of a batch fixed across its n_future unroll (train.py:90-108), so this is per batch."""
+    training loop keeps the edges of a batch fixed across its n_future unroll (train.py:90-108), so this is per batch.
+    `device_views`: the sender-side arrays (send_perm, col_ptr) from ONE launch of ag_edge_views, enqueued in front of the host read,
+    instead of torch.sort + bincount + cumsum behind it — the same arrays element for element (the differentiable rollouts build
+    their views once per model step)."""
 
-    def __init__(self, csr: CSREdges):
+    def __init__(self, csr: CSREdges, device_views=False):
         self.M = csr.B * csr.N
         self.row_ptr = csr.row_ptr.contiguous()
+        if device_views:
+            _require_gpu(self.row_ptr, "row_ptr")
+            dev = self.row_ptr.device
+            send_all = csr.edge_send.contiguous()
+            perm = torch.empty(max(send_all.numel(), 1), dtype=torch.int32, device=dev)
+            self.col_ptr = torch.empty(self.M + 1, dtype=torch.int32, device=dev)
+            ws = workspace(dev, _lib.lib().ag_edge_views_workspace_bytes(csr.B, csr.N))
+            _lib.call("ag_edge_views", dev, self.row_ptr, send_all, csr.B, csr.N, self.col_ptr, perm, ws)
         self.E = int(self.row_ptr[-1].item())
         self.recv = csr.edge_recv[: self.E].contiguous()
         self.send = csr.edge_send[: self.E].contiguous()
+        if device_views:
+            self.send_perm = perm[: self.E]
+            return
         send64 = self.send.long()
         self.send_perm = torch.sort(send64, stable=True).indices.to(torch.int32).contiguous()
         counts = torch.bincount(send64, minlength=self.M)

@@ -569,6 +569,41 @@ int ag_message_forward(const float *eterm, const float *hr, const float *hs, con
 int ag_message_backward(const float *eterm, const float *hr, const float *hs, const int32_t *row_ptr, const int32_t *send,
                         const float *grad_agg, float *grad_edge, float *grad_hr, int64_t n_nodes, int D, ag_stream_t stream);
 
+/* ag_edge_views: the SENDER-side view of a receiver-sorted edge list, on the device in one launch — what the autograd of the one-hot Rs.bmm
+ * gathers (model.py:224-249, 283-284: their backward is Rs^T.bmm) needs as (pointer, permutation), and what torch.sort(stable) + bincount +
+ * cumsum built before:
+ *   send_perm (n_edges) = the edges in ascending sender order, equal senders in ascending edge order (a stable argsort of edge_send),
+ *   col_ptr (B*N + 1)   = exclusive prefix of the per-sender edge counts, col_ptr[B*N] = n_edges = row_ptr[B*N].
+ * row_ptr (B*N + 1) and edge_send are those of ag_build_edges: sample b's edges are [row_ptr[bN], row_ptr[(b+1)N]) and their senders lie in
+ * [bN, (b+1)N) (an edge whose sender does not is skipped, and its slot of send_perm left unwritten).  One workgroup per sample: a counting
+ * sort with integer counters only, so the result does not depend on any order of execution.  No memset, no host synchronisation, no
+ * allocation: capturable.  `workspace`: ag_edge_views_workspace_bytes(B, N) bytes (the counters of samples too large for LDS; may be 0). */
+size_t ag_edge_views_workspace_bytes(int B, int N);
+int ag_edge_views(const int32_t *row_ptr, const int32_t *edge_send, int B, int N, int32_t *col_ptr, int32_t *send_perm, void *workspace,
+                  ag_stream_t stream);
+
+/* ag_step_update_forward / ag_step_update_backward: the tail of a model step of the DIFFERENTIABLE rollouts, out of place, and its adjoint —
+ * one launch each (forward_dynamics.py:160-176 of dynamics / :356-372 of dynamics_masked under autograd; ag_rollout's in-place step update
+ * is the no-grad form):
+ *   rec_out[b]          = repeat[b] == step ? pred[b] : rec[b]                                   record-on-repeat      (rec may be NULL: zeros)
+ *   y[b]                = min_i pred[b,i,1] (AG_HEIGHT_MIN) | sum_i pred[b,i,1] m[b,i] / sum_i m[b,i] (AG_HEIGHT_MASKED_MEAN, m = obj_mask) ; + raise
+ *   state_out[b,h]      = state[b,h+1] (h < H-1);  state_out[b,H-1] = [pred[b] | tool rows: (state[b,H-1].x + delta.x, y[b], state[b,H-1].z + delta.z)]
+ * pred (B,n_p,3), state / state_out (B,H,N,3), delta (B,N,3), rec / rec_out (B,n_p,3), repeat (B), obj_mask (B,n_p) bytes; the tool rows are
+ * the last N - n_p of a sample.  The sums run in ag_rollout's order (thread-strided partials, xor butterfly, (w0 + w1) + (w2 + w3)).
+ * Backward, given grad_state_out and grad_rec_out:
+ *   grad_rec   = repeat[b] == step ? 0 : grad_rec_out
+ *   grad_state[b,h] = grad_state_out[b,h-1] (h >= 1; the oldest frame's gradient is dropped by the shift) + the tool rows' x / z of
+ *                     grad_state_out[b,H-1] at h = H-1;  grad_delta = those tool x / z, zero elsewhere
+ *   grad_pred  = (grad_state_out[b,H-1,:n_p] + [repeat[b] == step] grad_rec_out[b]) + the height's share in y: with G[b] the sum of the tool
+ *                rows' y gradients, G to the FIRST particle that attains the minimum (AG_HEIGHT_MIN), G / count to every masked-in particle
+ *                (AG_HEIGHT_MASKED_MEAN).
+ * One fixed summation order per output, no atomics: the same bits on every call. */
+int ag_step_update_forward(const float *pred, const float *state, const float *delta, const float *rec, const int32_t *repeat, const uint8_t *obj_mask,
+                           int B, int H, int N, int n_p, int step, int height_mode, float raise, float *state_out, float *rec_out, ag_stream_t stream);
+int ag_step_update_backward(const float *pred, const int32_t *repeat, const uint8_t *obj_mask, int B, int H, int N, int n_p, int step, int height_mode,
+                            const float *grad_state_out, const float *grad_rec_out, float *grad_pred, float *grad_state, float *grad_delta,
+                            float *grad_rec, ag_stream_t stream);
+
 /* ---- training path, dense stacks (row n4): the Linear(+ReLU) chains of DynamicsPredictor.forward and their backward as fused
  * MFMA kernels (activations stay in registers between layers, in both directions; arithmetic per call: `precision` below — the
  * Python training path defaults to split-bf16).  Replaces the forward/backward of
