@@ -26,8 +26,9 @@ def tg(a):
 
 def cost_matrix(x, y):
     """(N,3), (M,3) -> (N,M) fp32: c = sqrt((dx dx + dy dy) + dz dz), every product rounded to fp32 on its own."""
-    d = x[:, None, :].astype(np.float32) - y[None, :, :].astype(np.float32)
-    return np.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]).astype(np.float32)
+    x, y = x.astype(np.float32), y.astype(np.float32)
+    d0, d1, d2 = (x[:, None, c] - y[None, :, c] for c in range(3))       # (one contiguous (N,M) plane per coordinate: the same operations)
+    return np.sqrt((d0 * d0 + d1 * d1) + d2 * d2).astype(np.float32)
 
 
 def inverse(col, M):
@@ -54,9 +55,10 @@ def expected_value(x, y, col):
     return out
 
 
-def case(name, broadcast=False):
-    """x, y, xm, ym, col of a fixture case; broadcast: y[:1] (and ym[:1]) for every sample, with the assignment recorded for that."""
-    g = golden()
+def case(name, broadcast=False, g=None):
+    """x, y, xm, ym, col of a fixture case; broadcast: y[:1] (and ym[:1]) for every sample, with the assignment recorded for that.
+    g: the loaded fixture file, gnn_loss_cases by default."""
+    g = golden() if g is None else g
     x, y = g[name + "_x"], g[name + "_y"]
     xm, ym = (g[name + "_xm"], g[name + "_ym"]) if name + "_xm" in g else (None, None)
     if broadcast:
@@ -297,8 +299,39 @@ def test_refusals_launch_nothing():
 
 
 # ------------------------------------------------------------------ 10: hausdorff
-def hausdorff_numpy(x, y, xm, ym):
-    """values (B,2) fp32 and arg (B,4) by the formula in numpy fp32; np.argmax / np.argmin return the first (lowest) index."""
+def hausdorff_numpy(x, y, xm, ym, rows=512):
+    """values (B,2) fp32 and arg (B,4) by the formula in numpy fp32, the cost matrix evaluated `rows` valid x points at a time (at the size limit
+    the whole matrix and its temporaries would be hundreds of MB).  np.argmax / np.argmin return the first (lowest) index inside a block; across
+    blocks a later block replaces a running minimum only when strictly lower and the running maximum only when strictly higher, so the lowest
+    index wins as in `hausdorff_numpy_whole`."""
+    B = x.shape[0]
+    val, arg = np.full((B, 2), np.nan, np.float32), np.full((B, 4), -1, np.int32)
+    for b in range(B):
+        by = b if y.shape[0] == B else 0
+        vx = np.arange(x.shape[1]) if xm is None else np.flatnonzero(xm[b])
+        vy = np.arange(y.shape[1]) if ym is None else np.flatnonzero(ym[by])
+        if len(vx) == 0 or len(vy) == 0:
+            continue
+        yv = y[by][vy]
+        best, bn, bm = np.float32(-1.0), -1, -1                           # max_n min_m with its n and that n's nearest m (compact positions)
+        cmin, carg = np.full(len(vy), np.inf, np.float32), np.full(len(vy), -1, np.int64)      # min_n per m so far, and its n
+        for i0 in range(0, len(vx), rows):
+            C = cost_matrix(x[b][vx[i0:i0 + rows]], yv)
+            rmin = C.min(1)
+            n = int(np.argmax(rmin))
+            if rmin[n] > best:
+                best, bn, bm = rmin[n], i0 + n, int(np.argmin(C[n]))
+            blk, blk_arg = C.min(0), C.argmin(0)
+            lower = blk < cmin
+            cmin[lower], carg[lower] = blk[lower], i0 + blk_arg[lower]
+        m = int(np.argmax(cmin))
+        val[b] = best, cmin[m]
+        arg[b] = vx[bn], vy[bm], vy[m], vx[carg[m]]
+    return val, arg
+
+
+def hausdorff_numpy_whole(x, y, xm, ym):
+    """`hausdorff_numpy` on the whole cost matrix at once: what the block-wise form is checked against on the CPU."""
     B = x.shape[0]
     val, arg = np.full((B, 2), np.nan, np.float32), np.full((B, 4), -1, np.int32)
     for b in range(B):

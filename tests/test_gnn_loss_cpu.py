@@ -70,6 +70,73 @@ def test_fixture_small_cases_are_optimal_by_brute_force():
     assert proved >= 4 * 3 * 2 + 3
 
 
+LARGE_CASES = ["s512x512", "s513x300", "s300x513", "s640x1024", "s1000x1000", "s1024x1024", "masked1024", "chain1024x1024", "chain513x1024"]
+
+
+def test_large_fixture_is_self_consistent():
+    """tests/golden/gnn_loss_large.npz (too large for brute force): every recorded assignment is an injection of the valid smaller side into
+    valid points of the other, its total is the ascending-n fp64 sum of the fp32 costs, and the optimum was unique for the generator."""
+    g = load_golden("gnn_loss_large")
+    assert os.path.getsize(os.path.join(ROOT, "tests", "golden", "gnn_loss_large.npz")) < 512 * 1024
+    assert [str(c) for c in g["cases"]] == LARGE_CASES
+    checked = 0
+    for name in LARGE_CASES:
+        x, y = g[name + "_x"], g[name + "_y"]
+        assert x.dtype == np.float32 and y.dtype == np.float32 and int(g[name + "_unique"]) == 1
+        if not name.startswith("chain"):                                  # Gaussian coordinates on the 2^-12 grid
+            assert np.array_equal(x * 4096, np.round(x * 4096)) and np.array_equal(y * 4096, np.round(y * 4096))
+        xm, ym = (g[name + "_xm"], g[name + "_ym"]) if name + "_xm" in g else (None, None)
+        forms = [(y, ym, g[name + "_col"], g[name + "_total"])]
+        if name.startswith("chain"):
+            assert x.shape[0] == 1 and name + "_colb" not in g
+        else:
+            forms.append((y[:1], None if ym is None else ym[:1], g[name + "_colb"], g[name + "_totalb"]))
+        for yy, yym, col, total in forms:
+            assert col.shape == x.shape[:2] and col.dtype == np.int32 and total.shape == x.shape[:1] and total.dtype == np.float64
+            for b in range(x.shape[0]):
+                by = b if yy.shape[0] == x.shape[0] else 0
+                vx = np.arange(x.shape[1]) if xm is None else np.flatnonzero(xm[b])
+                vy = np.arange(yy.shape[1]) if yym is None else np.flatnonzero(yym[by])
+                K = min(len(vx), len(vy))
+                if K == 0:
+                    assert np.isnan(total[b]) and (col[b] == -1).all()
+                    continue
+                n = np.flatnonzero(col[b] >= 0)
+                assert len(n) == K and np.isin(n, vx).all() and np.isin(col[b, n], vy).all() and len(set(col[b, n].tolist())) == K
+                assert col[b].max() < yy.shape[1] and (col[b][col[b] < 0] == -1).all()
+                C = cost_matrix(x[b], yy[by])
+                S = 0.0
+                for i in n:                                               # ascending n
+                    S += float(C[i, col[b, i]])
+                assert total[b] == S, (name, b)
+                checked += 1
+    assert checked == 6 * 2 * 2 + 4 + 4 + 2
+
+
+def test_block_wise_hausdorff_reference_equals_the_whole_matrix_one():
+    """The reference of the GPU tests evaluates the cost matrix in row blocks; block sizes that divide the cloud, do not, and exceed it give the
+    bits and the indices of the whole-matrix form, also where every minimum and maximum is attained many times."""
+    from test_gnn_loss import hausdorff_numpy, hausdorff_numpy_whole
+    g = load_golden("gnn_loss_cases")
+    x, y = g["s257x129_x"], g["s257x129_y"]
+    rng = np.random.default_rng(9)
+    gx, gy = rng.integers(0, 3, (2, 300, 3)).astype(np.float32), rng.integers(0, 3, (2, 280, 3)).astype(np.float32) + np.float32(0.5)
+    gx[:, 150:] = gx[:, :150]
+    gy[:, 140:] = gy[:, :140]
+    gxm, gym = (rng.random((2, 300)) < 0.6).astype(np.uint8), (rng.random((2, 280)) < 0.6).astype(np.uint8)
+    mx, my = g["masked_xm"], g["masked_ym"]
+    cases = [(x, y, None, None), (x, y[:1], None, None), (gx, gy, None, None), (gx, gy, gxm, gym), (gx, gy[:1], gxm, gym[:1]),
+             (g["masked_x"], g["masked_y"], mx, my)]
+    for cx, cy, cxm, cym in cases:
+        want_val, want_arg = hausdorff_numpy_whole(cx, cy, cxm, cym)
+        for rows in (1, 7, 50, 64, 257, 512):
+            val, arg = hausdorff_numpy(cx, cy, cxm, cym, rows=rows)
+            assert val.dtype == np.float32 and arg.dtype == np.int32
+            assert np.array_equal(val.view(np.int32), want_val.view(np.int32)) and np.array_equal(arg, want_arg), rows
+    tied_val, tied_arg = hausdorff_numpy_whole(gx, gy, None, None)
+    assert (tied_arg[:, [0, 3]] < 150).all() and (tied_arg[:, [1, 2]] < 140).all()      # (the grid does have its ties: duplicates never win)
+
+
 def test_loss_spec_parser():
     assert gnn_loss.parse_loss_spec([["mse", 1], ["emd", 0.5]]) == [("mse", 1.0), ("emd", 0.5)]
     assert gnn_loss.parse_loss_spec([("chamfer", 2), ("hausdorff", 0.25)]) == [("chamfer", 2.0), ("hausdorff", 0.25)]

@@ -2,7 +2,8 @@
 """Generate tests/golden/gnn_loss_cases.npz: inputs and expected results of the matching losses (adaptigraph_amd.losses.emd / hausdorff,
 adaptigraph_amd.gnn_loss), on the build machine only (needs scipy and the imported reference, as tools/gen_golden.py does).
 
-    python tools/gen_loss_golden.py
+    python tools/gen_loss_golden.py          # gnn_loss_cases.npz
+    python tools/gen_loss_golden.py large    # gnn_loss_large.npz: the same recording at 300 ... 1024 points (scipy only, its own seed)
 
 Per case `<name>` the file holds
     <name>_x (B,N,3), <name>_y (By,M,3) fp32, and for the masked cases <name>_xm (B,N), <name>_ym (By,M) u8;
@@ -14,7 +15,8 @@ Per case `<name>` the file holds
         with one y per sample;
     <name>_unique: 1 when the optimum is unique as far as three scipy solves can tell (on C, on C.T and on a row-permuted C: all three return
         the same pairs); the generator refuses to write a case it expects to be unique and is not.
-`cases` lists the names.  No test imports scipy or the reference: the small cases are re-proved by brute force in tests/test_gnn_loss_cpu.py.
+`cases` lists the names.  gnn_loss_large.npz holds the keys above (no `_ref`) for the cases of `LARGE_SHAPES`, `masked1024` and the two long chains:
+every register slot of the 8 and 16 columns-per-lane kernels, valid counts far below and across a size class.  No test imports scipy or the reference: the small cases are re-proved by brute force in tests/test_gnn_loss_cpu.py.
 """
 import os
 import sys
@@ -29,7 +31,11 @@ sys.path.insert(0, HERE)
 from ref_import import import_reference  # noqa: E402
 
 OUT = os.path.join(ROOT, "tests", "golden", "gnn_loss_cases.npz")
+OUT_LARGE = os.path.join(ROOT, "tests", "golden", "gnn_loss_large.npz")
 SHAPES = [(1, 1), (1, 5), (5, 1), (2, 3), (63, 64), (64, 65), (65, 64), (100, 100), (129, 257), (257, 129)]
+LARGE_SHAPES = [(512, 512), (513, 300), (300, 513), (640, 1024), (1000, 1000), (1024, 1024)]
+MASKED1024_COUNTS = [(700, 900), (0, 500), (3, 1024), (1024, 1), (513, 512)]
+LARGE_CHAINS = [(1024, 1024), (513, 1024)]
 
 
 def cost_matrix(x, y):
@@ -98,6 +104,39 @@ def record(out, name, x, y, rng, xm=None, ym=None, need_unique=True, broadcast=F
     out.setdefault("cases", []).append(name)
 
 
+def chain(N, M):
+    x, y = np.zeros((1, N, 3), np.float32), np.zeros((1, M, 3), np.float32)
+    x[0, :, 0] = np.arange(N, dtype=np.float32)[::-1]
+    y[0, :, 0] = np.arange(M, dtype=np.float32) + np.float32(0.4)
+    return x, y
+
+
+def main_large():
+    """The size classes the small file does not reach: 8 columns per lane with every slot occupied, 16 columns per lane from its first size to
+    the limit.  Its own rng stream, so gnn_loss_cases.npz does not depend on it."""
+    out = {}
+    rng = np.random.default_rng(20250611)
+    for N, M in LARGE_SHAPES:                                             # Gaussian clouds, two different samples each
+        x, y = gauss(rng, (2, N, 3)), gauss(rng, (2, M, 3))
+        record(out, f"s{N}x{M}", x, y, rng, broadcast=True)
+    # 1024 slots a side, the valid points scattered: few valid in many slots, the rows on either side, counts across the 512 boundary
+    N = M = 1024
+    B = len(MASKED1024_COUNTS)
+    x, y = gauss(rng, (B, N, 3)), gauss(rng, (B, M, 3))
+    xm, ym = np.zeros((B, N), np.uint8), np.zeros((B, M), np.uint8)
+    for b, (nx, my) in enumerate(MASKED1024_COUNTS):
+        xm[b, rng.permutation(N)[:nx]] = 1
+        ym[b, rng.permutation(M)[:my]] = 1
+    record(out, "masked1024", x, y, rng, xm, ym, broadcast=True)
+    for N, M in LARGE_CHAINS:                                             # augmenting paths through every register slot
+        record(out, f"chain{N}x{M}", *chain(N, M), rng)
+    for name in out["cases"]:
+        assert int(out[name + "_unique"]) == 1, name
+    out["cases"] = np.array(out["cases"])
+    np.savez_compressed(OUT_LARGE, **out)
+    print(f"{OUT_LARGE}: {len(out['cases'])} cases, {os.path.getsize(OUT_LARGE) / 1024:.1f} KiB")
+
+
 def main():
     import_reference()
     from dynamics.gnn import loss as ref
@@ -123,10 +162,7 @@ def main():
     record(out, "masked_small", x, y, rng, xm, ym)
     # the chain: x_n = (n, 0, 0), y_m = (m + 0.4, 0, 0), the rows in descending order (every augmentation walks the whole chain)
     for N, M in ((64, 64), (65, 130)):
-        x, y = np.zeros((1, N, 3), np.float32), np.zeros((1, M, 3), np.float32)
-        x[0, :, 0] = np.arange(N, dtype=np.float32)[::-1]
-        y[0, :, 0] = np.arange(M, dtype=np.float32) + np.float32(0.4)
-        record(out, f"chain{N}x{M}", x, y, rng)
+        record(out, f"chain{N}x{M}", *chain(N, M), rng)
     # near-rigid: y = a permutation of x + 0.01 noise; the assignment recovers the permutation
     x = gauss(rng, (3, 100, 3))
     perm = np.stack([rng.permutation(100) for _ in range(3)])
@@ -149,4 +185,9 @@ def main():
 
 
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["large"]:
+        main_large()
+    elif sys.argv[1:]:
+        raise SystemExit("usage: gen_loss_golden.py [large]")
+    else:
+        main()
