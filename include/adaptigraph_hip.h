@@ -508,6 +508,26 @@ int ag_cloud_outlier_filter(const float *pts, const int32_t *count, int n_max, c
 int ag_cloud_select(const float *pts, const int32_t *count, int n_max, const uint8_t *flags, const float *z_below, float *out, int32_t *count_out,
                     void *workspace, size_t workspace_bytes, ag_stream_t stream);
 
+/* ---- rope push simulator (the data side; stands in for what src/sim/sim_env/flex_env.py:258-402 asks of its closed particle solver): ONE push
+ * of E rope-on-table episodes in one launch, one 256-thread workgroup per episode, one particle per thread.  The model is this project's own
+ *  and is stated operation for operation by adaptigraph_amd/sim.py:rope_push_host; the kernel gives the same bits.
+ * Per-episode DEVICE arrays, (E) each: n particles in rope order (2 .. n_max), l0 rest spacing, w cluster width and kappa cluster gain (clusters
+ * are skipped when w < 3 or w > n), n_push steps of the push (1 .. n_push_max), inv = float(1 / (n_push substeps)); push (E,4) = xs, zs, xe, ze.
+ * State x, v (E,n_max,3) fp32, read and written in place (rows >= n untouched).  Per step `substeps` substeps of h seconds: predict under
+ * gravity g, stretch (even pairs, then odd pairs), straight-segment shape matching, the cylindrical pusher of radius R against particles of radius
+ * r (push steps only), the ground at height r, velocities with Coulomb friction mu on grounded particles; after the n_push steps `settle` steps
+ * without the pusher.  Out: obj (E,F_max,n_max,3) and eef (E,F_max,3): frame f holds x and the pusher point (c.x, r, c.z) after push step
+ * f record_every, the episode's last frame x after the settle with the pusher point (xe, r + lift, ze); n_frames (E) = (n_push - 1) /
+ * record_every + 2 frames written, rows and frames behind them untouched.
+ * AG_ERR_ARG, nothing launched: a null pointer, n_max outside 2 .. AG_SIM_ROPE_MAX_PARTICLES, F_max < (n_push_max - 1) / record_every + 2,
+ * substeps or record_every < 1.  n_max and n_push_max are the host's bounds on the device arrays: an episode whose n or n_push lies outside
+ * them writes n_frames = 0 and nothing else.  No host synchronisation, no atomics, the same bits on every call: safe to capture. */
+#define AG_SIM_ROPE_MAX_PARTICLES 256
+int ag_sim_rope_push(const int32_t *n, const float *l0, const int32_t *w, const float *kappa, const float *inv, const int32_t *n_push,
+                     const float *push, float *x, float *v, float *obj, float *eef, int32_t *n_frames, int E, int n_max, int F_max,
+                     int n_push_max, int substeps, int record_every, int settle, float h, float g, float r, float R, float mu, float lift,
+                     ag_stream_t stream);
+
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
  *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
