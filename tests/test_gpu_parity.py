@@ -99,7 +99,7 @@ def test_edges_golden_exact(name):
     ("cloth", 4096, 2, "batch", {}),                           # configs[3]: connect_tools_all, N = 4097
     ("cloth", 4096, 1, "single", {}),
     ("cloth", 1024, 2, "batch", dict(tool_near=False)),
-    ("rope", 700, 2, "batch", dict(dense=True)),               # dense blob: > 384 in-radius candidates per row (prune path)
+    ("rope", 700, 2, "batch", dict(dense=True)),               # dense blob: > 384 in-radius candidates per row, through the packed top-10 kernel (no candidate list; the in-loop prune: test_edge_paths.py, `blob`)
 ])
 def test_edges_vs_oracle_exact(material, n_obj, batch, variant, kw):
     dense = kw.pop("dense", False) if isinstance(kw, dict) else False
