@@ -136,6 +136,8 @@ SIGNATURES = {
     "ag_cloud_select": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
     # rope push simulator
     "ag_sim_rope_push": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float] * 6 + [c_void_p]),
+    # granular push simulator
+    "ag_sim_pile_push": (c_int, [c_void_p] * 11 + [c_int] * 8 + [c_float] * 9 + [c_void_p]),
     # training batches assembled on the device
     "ag_gather_clouds": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3),
     "ag_assemble_batch": (c_int, [P(BatchDims)] + [c_void_p] * 8 + [P(BatchOut), c_void_p]),

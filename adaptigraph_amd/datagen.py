@@ -1,13 +1,18 @@
-"""Rope push datasets from the particle simulator (sim.py), written in the layout `load.py` reads — the work of the reference's
-src/sim/data_gen/data_gen.py followed by src/dynamics/preprocess/preprocess.py:135-230, for rope, without the .h5 files in between.
+"""Rope and granular push datasets from the particle simulator (sim.py), written in the layout `load.py` reads — the work of the reference's
+src/sim/data_gen/data_gen.py followed by src/dynamics/preprocess/preprocess.py:135-230, without the .h5 files in between.
 
-    python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5
+    python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5                          # rope
+    python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5 --material granular
 
     DIR/sim_data/rope/<episode:06>/property_params.pkl          {'particle_radius', 'stiffness'}
     DIR/preprocess/rope/frame_pairs/<episode:06>_<push:02>.txt  rows of n_his + n_future frame indices (preprocess.extract_push)
     DIR/preprocess/rope/positions.pkl                           {'eef_pos': [(T, 1, 3)], 'obj_pos': [(T, n, 3)]} float32, one entry per episode
     DIR/preprocess/rope/phys_range.txt                          min and max of the stiffness
     DIR/preprocess/rope/metadata.txt                            dist_thresh,n_future,n_his
+
+With --material granular the same tree under .../granular/: property_params.pkl holds {'particle_radius', 'granular_scale', 'num_granular'},
+eef_pos entries are (T, 5, 3) (the board's five key points), obj_pos entries (T, n_e, 3) with n_e grains in episode e, phys_range.txt the
+range of granular_scale.
 """
 import argparse
 import os
@@ -28,21 +33,79 @@ def default_dataset_config():
     return dict(configs.dataset_config("rope"), dist_thresh=DIST_THRESH)
 
 
+# A board push records the same frames (speed 0.01, a frame every 10 steps: 0.0988 .. 0.1 of travel each).  The reference's granular threshold
+# (config/dynamics/granular.yaml:12: 0.2) sits just ABOVE two frames' travel, for the reason above, and would make every tuple step by three
+# frames; the default here sits just under two frames of the shortest sampled push (2 x 0.0988) and well above one frame (< 0.1): mid-push
+# rows step by exactly two frames.
+GRANULAR_DIST_THRESH = 0.19
+
+
+def default_granular_dataset_config():
+    return dict(configs.dataset_config("granular"), dist_thresh=GRANULAR_DIST_THRESH)
+
+
+def _write_dataset(root, ds, properties, phys, pairs, eef_pos, obj_pos):
+    """The files of one dataset: properties (one dict per episode), phys (E) the physics parameter, pairs {(e, k): rows}, positions per episode."""
+    name = ds["data_name"]
+    data_dir, prep_dir = os.path.join(root, "sim_data"), os.path.join(root, "preprocess")
+    pairs_dir = os.path.join(prep_dir, name, "frame_pairs")
+    os.makedirs(pairs_dir, exist_ok=True)
+    for (e, k), rows in pairs.items():
+        np.savetxt(os.path.join(pairs_dir, f"{e:06}_{k + 1:02}.txt"), rows, fmt="%d")
+    for e, prop in enumerate(properties):
+        os.makedirs(os.path.join(data_dir, name, f"{e:06}"), exist_ok=True)
+        with open(os.path.join(data_dir, name, f"{e:06}", "property_params.pkl"), "wb") as f:
+            pickle.dump(prop, f)
+    with open(os.path.join(prep_dir, name, "positions.pkl"), "wb") as f:
+        pickle.dump({"eef_pos": [np.concatenate(p) for p in eef_pos], "obj_pos": [np.concatenate(p) for p in obj_pos]}, f)
+    phys = np.asarray(phys).astype(np.float32)[:, None]
+    np.savetxt(os.path.join(prep_dir, name, "phys_range.txt"), np.stack([phys.min(0), phys.max(0)]))
+    with open(os.path.join(prep_dir, name, "metadata.txt"), "w") as f:
+        f.write(f"{ds['dist_thresh']},{ds['n_future']},{ds['n_his']}")
+    return dict(ds, data_dir=data_dir, prep_data_dir=prep_dir)
+
+
+def generate_granular_dataset(root, n_episodes, n_pushes, seed=0, device=None, dataset_config=None, params=sim.PILE_DEFAULT,
+                              area_range=(1.0, 9.0)):
+    """Simulate n_episodes piles through n_pushes board pushes each and write the dataset under `root`.  Episode e draws its pile
+    (`sim.initial_pile`: its granular_scale, and with it its number of grains) and its pushes (`sim.sample_board_push`) from
+    numpy.random.default_rng(seed + e); push k of ALL episodes, whatever their numbers of grains, is one `sim.pile_push` call on `device`, read
+    back once.  device=None runs the host statement `sim.pile_push_host` instead: the same files with the same bytes.
+    -> dataset_config with data_dir / prep_data_dir filled in."""
+    ds = dict(default_granular_dataset_config() if dataset_config is None else dataset_config)
+    rngs = [np.random.default_rng(seed + e) for e in range(n_episodes)]
+    piles, scales = zip(*(sim.initial_pile(rng, area_range) for rng in rngs))
+    scene = sim.PileScene.from_piles(piles, [s / 2 for s in scales])
+    eef_pos, obj_pos, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes, {}
+    for k in range(n_pushes):
+        push = np.stack([sim.sample_board_push(scene.x[e, :scene.n[e]], scene.rho[e], rngs[e], params) for e in range(n_episodes)])
+        if device is None:
+            obj, eef, nf, x, v = sim.pile_push_host(scene, push, params)
+        else:
+            obj, eef, nf, x, v = (t.cpu().numpy() for t in sim.pile_push(scene, push, params, device=device))
+        scene.x, scene.v = x, v
+        for e in range(n_episodes):
+            tool = eef[e, :nf[e]]
+            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
+            n_frames[e] += cnt
+            eef_pos[e].append(tool)
+            obj_pos[e].append(obj[e, :nf[e], :scene.n[e]])
+    properties = [{"particle_radius": float(scene.rho[e]), "granular_scale": float(scales[e]), "num_granular": int(scene.n[e])}
+                  for e in range(n_episodes)]
+    return _write_dataset(root, ds, properties, scales, pairs, eef_pos, obj_pos)
+
+
 def generate_rope_dataset(root, n_episodes, n_pushes, seed=0, device=None, dataset_config=None, n_particles=128, params=sim.DEFAULT):
     """Simulate n_episodes ropes of n_particles particles through n_pushes pushes each and write the dataset under `root`.  Episode e draws its
     rope, its stiffness and its pushes from numpy.random.default_rng(seed + e) (data_gen.py:27 seeds per episode); push k of ALL episodes is one
     `sim.rope_push` call on `device`, read back once, after which the next pushes are drawn on the host.  device=None runs the host
     restatement `sim.rope_push_host` instead: the same files with the same bytes.  -> dataset_config with data_dir / prep_data_dir filled in."""
     ds = dict(default_dataset_config() if dataset_config is None else dataset_config)
-    name = ds["data_name"]
-    data_dir, prep_dir = os.path.join(root, "sim_data"), os.path.join(root, "preprocess")
-    pairs_dir = os.path.join(prep_dir, name, "frame_pairs")
-    os.makedirs(pairs_dir, exist_ok=True)
     rngs = [np.random.default_rng(seed + e) for e in range(n_episodes)]
     ropes = [sim.initial_rope(rng, n_particles, params.r) for rng in rngs]
     stiffness = np.array([rng.uniform(0.0, 1.0) for rng in rngs])
     scene = sim.RopeScene.from_ropes(ropes, stiffness=stiffness)
-    eef_pos, obj_pos, n_frames = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes
+    eef_pos, obj_pos, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes, {}
     for k in range(n_pushes):
         push = np.stack([sim.sample_push(scene.x[e, :scene.n[e]], rngs[e], params) for e in range(n_episodes)])
         if device is None:
@@ -52,22 +115,12 @@ def generate_rope_dataset(root, n_episodes, n_pushes, seed=0, device=None, datas
         scene.x, scene.v = x, v
         for e in range(n_episodes):
             tool = eef[e, :nf[e], None, :]
-            rows, cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
-            np.savetxt(os.path.join(pairs_dir, f"{e:06}_{k + 1:02}.txt"), rows, fmt="%d")
+            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
             n_frames[e] += cnt
             eef_pos[e].append(tool)
             obj_pos[e].append(obj[e, :nf[e], :scene.n[e]])
-    for e in range(n_episodes):
-        os.makedirs(os.path.join(data_dir, name, f"{e:06}"), exist_ok=True)
-        with open(os.path.join(data_dir, name, f"{e:06}", "property_params.pkl"), "wb") as f:
-            pickle.dump({"particle_radius": float(params.r), "stiffness": float(stiffness[e])}, f)
-    with open(os.path.join(prep_dir, name, "positions.pkl"), "wb") as f:
-        pickle.dump({"eef_pos": [np.concatenate(p) for p in eef_pos], "obj_pos": [np.concatenate(p) for p in obj_pos]}, f)
-    phys = stiffness.astype(np.float32)[:, None]
-    np.savetxt(os.path.join(prep_dir, name, "phys_range.txt"), np.stack([phys.min(0), phys.max(0)]))
-    with open(os.path.join(prep_dir, name, "metadata.txt"), "w") as f:
-        f.write(f"{ds['dist_thresh']},{ds['n_future']},{ds['n_his']}")
-    return dict(ds, data_dir=data_dir, prep_data_dir=prep_dir)
+    properties = [{"particle_radius": float(params.r), "stiffness": float(stiffness[e])} for e in range(n_episodes)]
+    return _write_dataset(root, ds, properties, stiffness, pairs, eef_pos, obj_pos)
 
 
 def main(argv=None):
@@ -75,12 +128,17 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="dataset root")
     ap.add_argument("--episodes", type=int, default=64)
     ap.add_argument("--pushes", type=int, default=5)
-    ap.add_argument("--particles", type=int, default=128)
+    ap.add_argument("--material", choices=("rope", "granular"), default="rope")
+    ap.add_argument("--particles", type=int, default=128, help="rope only; a pile's number of grains follows from its scene")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0", help="a GPU, or 'host' for the numpy restatement (slow)")
     args = ap.parse_args(argv)
-    ds = generate_rope_dataset(args.out, args.episodes, args.pushes, args.seed, None if args.device == "host" else args.device,
-                               n_particles=args.particles)
+    device = None if args.device == "host" else args.device
+    if args.material == "granular":
+        ds = generate_granular_dataset(args.out, args.episodes, args.pushes, args.seed, device)
+        print(f"{args.episodes} episodes x {args.pushes} pushes of granular piles under {ds['data_dir']} and {ds['prep_data_dir']}")
+        return
+    ds = generate_rope_dataset(args.out, args.episodes, args.pushes, args.seed, device, n_particles=args.particles)
     print(f"{args.episodes} episodes x {args.pushes} pushes of {args.particles} particles under {ds['data_dir']} and {ds['prep_data_dir']}")
 
 

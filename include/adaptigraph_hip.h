@@ -528,6 +528,28 @@ int ag_sim_rope_push(const int32_t *n, const float *l0, const int32_t *w, const 
                      int n_push_max, int substeps, int record_every, int settle, float h, float g, float r, float R, float mu, float lift,
                      ag_stream_t stream);
 
+/* ---- granular push simulator (the data side for the granular material): ONE board push of E disc-pile episodes in one launch, one 256-thread
+ * workgroup per episode, four grains per thread, contacts through a 64 x 64 cell grid in LDS that is rebuilt before every contact iteration.
+ * The model is this project's own, stated operation for operation by adaptigraph_amd/sim.py:pile_push_host; the kernel gives
+ * the same bits.  Per-episode DEVICE arrays, (E) each: n discs (1 .. n_max), rho their radius (0 < rho <= rho_max), n_push steps of the push
+ * (1 .. n_push_max), inv = float(1 / (n_push substeps)); push (E,4) = xs, zs, xe, ze; lat (E,2) = the unit vector along the board (across the
+ * push).  State x, v (E,n_max,3) fp32, read and written in place: components x and z of rows < n; y is carried, rows >= n are untouched.
+ * Per step `substeps` substeps of h seconds: predict; `iters` Jacobi contact iterations between all discs nearer than 2 rho (integer sums of
+ * the corrections scaled by 2^22, divided by the number of contacts); the board of half width W and half thickness T (push steps only), which
+ * puts a disc nearer than rho + T to its segment at rho + T + slack from it; velocities with Coulomb friction mu under gravity g on every disc;
+ * after the n_push steps `settle` steps without the board.  Out: obj (E,F_max,n_max,3) and eef (E,F_max,5,3): frame f holds x and the board's
+ * key points c + (W o_k) lat, o = 1, -1, 0, 1/2, -1/2, at height tool_y after push step f record_every; the episode's last frame x after the
+ * settle with the key points at the push end, at tool_y + lift; n_frames (E) = (n_push - 1) / record_every + 2, rows and frames behind untouched.
+ * AG_ERR_ARG, nothing launched: a null pointer, n_max outside 1 .. AG_SIM_PILE_MAX_PARTICLES, F_max < (n_push_max - 1) / record_every + 2,
+ * substeps, iters or record_every < 1, rho_max outside (0, 0.25] (the bound under which the integer sums cannot overflow).  n_max, n_push_max
+ * and rho_max are the host's bounds on the device arrays: an episode whose n, n_push or rho lies outside them writes n_frames = 0 and nothing
+ * else.  No host synchronisation, integer LDS atomics only, the same bits on every call: safe to capture. */
+#define AG_SIM_PILE_MAX_PARTICLES 1024
+int ag_sim_pile_push(const int32_t *n, const float *rho, const float *inv, const int32_t *n_push, const float *push, const float *lat, float *x,
+                     float *v, float *obj, float *eef, int32_t *n_frames, int E, int n_max, int F_max, int n_push_max, int substeps, int iters,
+                     int record_every, int settle, float h, float g, float mu, float W, float T, float slack, float tool_y, float lift,
+                     float rho_max, ag_stream_t stream);
+
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
  *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
