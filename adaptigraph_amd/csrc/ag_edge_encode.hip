@@ -178,9 +178,10 @@ void ag_launch_edge_encode(const AgWeights &w, const AgFwdArgs &a, const AgPath 
     if (a.e_cap <= 0) return;
     const dim3 block(AG_MLP_THREADS);
     const int e_max = a.e_cap + a.self_rows;      // upper bound of the rows this launch encodes (the true count is on the device)
+    const int h3_cus = a.max_blocks / AG_MLP_WG_PER_CU > 0 ? a.max_blocks / AG_MLP_WG_PER_CU : 1;      // (max_blocks 1: one CU's worth, not an empty grid)
     switch (p.edge) {
     case AG_EDGE_H3_WS: ag_launch_edge_encode_ws(w, a, p, s); return;
-    case AG_EDGE_H3: hipLaunchKernelGGL(edge_encode_kernel<PrecH3>, dim3(grid_for(e_max, a.max_blocks / AG_MLP_WG_PER_CU * AG_H3_WG_PER_CU)), block, 0, s, w, a); return;
+    case AG_EDGE_H3: hipLaunchKernelGGL(edge_encode_kernel<PrecH3>, dim3(grid_for(e_max, h3_cus * AG_H3_WG_PER_CU)), block, 0, s, w, a); return;
     case AG_EDGE_B3: hipLaunchKernelGGL(edge_encode_kernel<PrecB3>, dim3(grid_for(e_max, a.max_blocks)), block, 0, s, w, a); return;
     case AG_EDGE_F32: hipLaunchKernelGGL(edge_encode_kernel<PrecF32>, dim3(grid_for(e_max, a.max_blocks)), block, 0, s, w, a); return;
     }

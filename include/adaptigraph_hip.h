@@ -67,7 +67,10 @@ int ag_model_destroy(ag_model *m);
  *                            workload, see ag_rollout_streams_for
  *   "fuse_aggregate"   0/2   segment reduce as its own HBM-streaming kernel (0, default) or inside node_update through an LDS stage
  *                            (2, precision 2 only, other modes keep the launch: no `agg` table; measured equal solo, -4 % in the two-stream rollout); bit-identical results
- *   "max_blocks"       n >= 1 persistent grid size (default 2 x #CUs)
+ *   "max_blocks"       n >= 1 persistent grid size (default 2 x #CUs): the workgroups of the streaming MLP kernels, n / 2 (at least one) of the
+ *                            weight-stationary ones; a rollout part takes its share n / parts.  No kernel reduces across workgroups, so a row's
+ *                            result does not depend on which workgroup computes it: bit-identical results for ANY value, down to one workgroup
+ *                            walking every block (tests/test_persistent_trips.py)
  *   "edge_products"    2/3   precision 2 only: arithmetic of the EDGE stack: 2 = fp16 (default: split-fp16 weights x fp16 activations + an e5m2
  *                            residual byte per activation, three fp16 MFMAs per fp32 product; models whose edge weights exceed the fp16 range
  *                            keep 3), 3 = split-bf16 like precision 1
