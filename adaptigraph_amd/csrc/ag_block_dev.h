@@ -1,5 +1,5 @@
-// ag_block_dev.h — the wave (64 lanes) and workgroup (256 threads = four waves) collectives of the kernels, written once.  No kernels here and
-// nothing of the engine.  What each primitive guarantees, and every caller relies on:
+// ag_block_dev.h — the wave (64 lanes) and workgroup (256 threads = four waves; block_min_u64: up to sixteen waves) collectives of the
+// kernels, written once.  No kernels here and nothing of the engine.  What each primitive guarantees, and every caller relies on:
 //   integers  — ranks, counts, scans, offsets: exact, whatever the order of the additions.
 //   floats    — ONE fixed order, so a result is the same bits on every call and in a replayed graph: a thread's own accumulation is the
 //               caller's; a wave is the xor butterfly with offsets 32, 16, .. 1; the four wave values of a workgroup are (w0 + w1) + (w2 + w3),
@@ -80,6 +80,30 @@ __device__ T block_exclusive_scan(T v, T *total)
     *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
     __syncthreads();
     return base + x - v;
+}
+
+// ---- minimum of a 64-bit key over a workgroup of ANY whole number of waves up to sixteen (1024 threads) ----
+// returns the smallest v of all threads, in every thread: an integer minimum, exact in any order, so a key (value bits) << 32 | index picks
+// the smallest value and, among equal values, the lowest index.  Every thread of the workgroup must call it.  Two barriers, the second behind
+// the last read of the function's LDS words: it may be called again at once.
+__device__ __forceinline__ unsigned long long min_u64(unsigned long long a, unsigned long long b) { return b < a ? b : a; }
+__device__ __forceinline__ unsigned long long lanes_xor(unsigned long long v, int o)
+{
+    const unsigned lo = __shfl_xor((unsigned)v, o), hi = __shfl_xor((unsigned)(v >> 32), o);
+    return ((unsigned long long)hi << 32) | lo;
+}
+__device__ unsigned long long block_min_u64(unsigned long long v)
+{
+    __shared__ unsigned long long wmin[16];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, waves = (int)(blockDim.x >> 6);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min_u64(v, lanes_xor(v, o));
+    if (lane == 0) wmin[wave] = v;
+    __syncthreads();
+    unsigned long long m = wmin[0];
+    for (int w = 1; w < waves; ++w) m = min_u64(m, wmin[w]);
+    __syncthreads();
+    return m;
 }
 
 // ---- two-pass scan over a grid: kScanRows items per workgroup ----

@@ -553,6 +553,35 @@ int ag_sim_pile_push(const int32_t *n, const float *rho, const float *inv, const
                      int record_every, int settle, float h, float g, float mu, float W, float T, float slack, float tool_y, float lift,
                      float rho_max, ag_stream_t stream);
 
+/* ---- cloth grasp-and-drag simulator (the data side for the cloth material): ONE grasp-and-drag of E mass-spring cloth episodes in one launch,
+ * one 1024-thread workgroup per episode, four particles per thread, the predicted positions in LDS.  The model is this project's own (NOT
+ * FleX, no self-collision), stated operation for operation by adaptigraph_amd/sim.py:cloth_push_host; the kernel gives the
+ * same bits.  A cloth is a grid of nx x nz particles, i = iz nx + ix.  Per-episode DEVICE arrays: nx, nz (E) in 2 .. 64 with nx nz <= n_max;
+ * rest (E,2) = l0, float(l0 sqrt 2); gains (E,4) = k_stretch, k_shear, k_bend, mu; steps (E,2) = n1, n2, the steps of the drag's two segments
+ * (each >= 1, n1 + n2 <= n_push_max); inv (E,2) = float(1 / (n substeps)) of each; action (E,4) = xs, zs, xe, ze; lat (E,2) = the horizontal
+ * unit vector across the drag.  State x, v (E,n_max,3) fp32, read and written in place (rows >= nx nz untouched).
+ * The gripper moves from (xs, 0, zs) to (xe, lift, ze) in n1 steps, then down to (xe, 0, ze) in n2 steps (heights above the grasp height), then
+ * lets go; `settle` steps follow.  The pick, on the x the call starts from: the up to AG_SIM_CLOTH_PICK_K particles of smallest
+ * d2 = dx dx + dz dz to (xs, zs), equal d2 decided by the lower index, are grasped if the smallest d2 <= grasp2 (none otherwise); a grasped
+ * particle keeps its offset from the gripper and is set to it every substep with inverse mass 0 until the release.
+ * Per step `substeps` substeps of h seconds: predict under gravity g with v scaled by damp; the pins; `iters` sweeps of the distance
+ * constraints -- stretch (ix, ix + 1), (iz, iz + 1) at l0, both diagonals of every cell at rest[1], bend (ix, ix + 2), (iz, iz + 2) at 2 l0 -- as
+ * twelve conflict-free phases in place (coloured Gauss-Seidel; sim.py has the order), c = gain (len - rest) / (len (w_i + w_j)), skipped
+ * when len == 0 or w_i + w_j == 0; the ground at height r; velocities with Coulomb friction mu on grounded, unpinned particles.
+ * Out: obj (E,F_max,n_max,3) and eef (E,F_max,2,3): frame f holds x and the two finger points c +- finger lat at height tool_y + c.y after
+ * step f record_every of the n1 + n2; the episode's last frame x after the settle with the finger points at (xe, lift, ze);
+ * n_frames (E) = (n1 + n2 - 1) / record_every + 2, rows and frames behind untouched; picked (E,AG_SIM_CLOTH_PICK_K) the grasped particles in
+ * the order of the pick, -1 where none.
+ * AG_ERR_ARG, nothing launched: a null pointer, n_max outside 4 .. AG_SIM_CLOTH_MAX_PARTICLES, F_max < (n_push_max - 1) / record_every + 2,
+ * substeps, iters or record_every < 1.  n_max and n_push_max are the host's bounds on the device arrays: an episode whose nx, nz or steps lie
+ * outside them writes n_frames = 0 and nothing else.  No host synchronisation, no atomics, the same bits on every call: safe to capture. */
+#define AG_SIM_CLOTH_MAX_PARTICLES 4096
+#define AG_SIM_CLOTH_PICK_K 5
+int ag_sim_cloth_push(const int32_t *nx, const int32_t *nz, const float *rest, const float *gains, const int32_t *steps, const float *inv,
+                      const float *action, const float *lat, float *x, float *v, float *obj, float *eef, int32_t *n_frames, int32_t *picked,
+                      int E, int n_max, int F_max, int n_push_max, int substeps, int iters, int record_every, int settle, float h, float g,
+                      float r, float damp, float lift, float grasp2, float finger, float tool_y, ag_stream_t stream);
+
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
  *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
