@@ -1,0 +1,70 @@
+"""The closed planning loop of the reference (src/planning/plan.py:212-315) without its drawing: observe, plan, act, slide the action window,
+observe again, record, score, optionally identify the physics parameter.  The environment is anything with `SimEnv`'s surface
+(`get_state_cur(fps_radius, return_cloud=True)`, `step`, `step_gripper`, `task_config`), the planner anything with the
+`trajectory_optimization(state_cur, act_seq)` of `mpc.Planner` / `mpc.ChunkedPlanner` and an `n_look_ahead` attribute."""
+import os
+
+import numpy as np
+import torch
+
+
+def run_closed_loop(env, planner, criteria, n_actions, n_look_ahead, action_lower_lim, action_upper_lim, fps_radius, save_dir=None,
+                    ppm_optimizer=None, use_ppo=False):
+    """plan.py:212-315.  `criteria` maps a cloud (1, n, 3) in simulator units to a 0-d error tensor; action_lower_lim / action_upper_lim are
+    (action_dim,) tensors on the planner's device; the random draws are the reference's (`torch.rand` for the first window, then one row per
+    step).  With `save_dir` step i writes interaction_{i}.npz with the reference's keys (plan.py:286-295) -- act, act_all, state_pred,
+    state_pred_all, pcd_real, state_real, state_init -- which PhysicsParamOnlineOptimizer.optimize reads back; `use_ppo` calls
+    `ppm_optimizer.optimize(i, iterations=50)` after every step.  -> (res_act_seq (n_actions, action_dim), error_seq of n_actions + 1 floats:
+    the error before the first action and after every action).
+    The window of step i is min(n_actions - i, n_look_ahead) rows, so that act_all and state_pred_all have the length plan.py:284-285 asserts;
+    the reference shortens its window one step later and trips those assertions at the last step whenever n_look_ahead > 1 (its shipped
+    configurations use 1)."""
+    device = action_upper_lim.device
+    action_dim = action_upper_lim.shape[0]
+    full_look_ahead = int(n_look_ahead)
+    gripper = bool(env.task_config.get("gripper_enable", False))
+    if use_ppo and (ppm_optimizer is None or save_dir is None):
+        raise ValueError("run_closed_loop: use_ppo needs ppm_optimizer and save_dir (the optimizer reads the recorded interactions)")
+    if save_dir is not None:
+        os.makedirs(save_dir, exist_ok=True)
+
+    def numpy_of(x):
+        return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
+
+    def observe():
+        state, cloud = env.get_state_cur(fps_radius, return_cloud=True)
+        if not isinstance(state, torch.Tensor):
+            state = torch.from_numpy(np.ascontiguousarray(state, np.float32))
+        return state.to(device=device, dtype=torch.float32), numpy_of(cloud)
+
+    def error_of(cloud):
+        return float(criteria(torch.from_numpy(cloud)[None].to(device)).item())
+
+    act_seq = torch.rand((full_look_ahead, action_dim), device=device) * (action_upper_lim - action_lower_lim) + action_lower_lim
+    res_act_seq = torch.zeros((n_actions, action_dim), device=device)
+    error_seq = []
+    for i in range(n_actions):
+        window = min(n_actions - i, full_look_ahead)              # sliding window: never past the last action
+        act_seq = act_seq[:window]
+        planner.n_look_ahead = window
+        state_cur, obj_pcd = observe()
+        if i == 0:
+            error_seq.append(error_of(obj_pcd))
+        res = planner.trajectory_optimization(state_cur, act_seq)
+        res = {k: v.detach().clone() if isinstance(v, torch.Tensor) else v for k, v in res.items()}
+        act = numpy_of(res["act_seq"][0])
+        (env.step_gripper if gripper else env.step)(act)
+        res_act_seq[i] = res["act_seq"][0].detach().clone()
+        act_seq = torch.cat([res["act_seq"][1:],
+                             torch.rand((1, action_dim), device=device) * (action_upper_lim - action_lower_lim) + action_lower_lim], dim=0)
+        state_real, pcd_real = observe()
+        if save_dir is not None:
+            pred = res["best_model_output"]["state_seqs"]
+            assert res["act_seq"].shape[0] == window and pred[0].shape[0] == window          # plan.py:284-285
+            np.savez(os.path.join(save_dir, f"interaction_{i}.npz"), act=act, act_all=numpy_of(res["act_seq"]), state_pred=numpy_of(pred[0, 0]),
+                     state_pred_all=numpy_of(pred[0]), pcd_real=pcd_real, state_real=numpy_of(state_real), state_init=numpy_of(state_cur))
+        error_seq.append(error_of(pcd_real))
+        if use_ppo:
+            ppm_optimizer.optimize(i, iterations=50)
+    planner.n_look_ahead = full_look_ahead
+    return res_act_seq, error_seq

@@ -582,6 +582,32 @@ int ag_sim_cloth_push(const int32_t *nx, const int32_t *nz, const float *rest, c
                       int E, int n_max, int F_max, int n_push_max, int substeps, int iters, int record_every, int settle, float h, float g,
                       float r, float damp, float lift, float grasp2, float finger, float tool_y, ag_stream_t stream);
 
+/* ---- simulated depth cameras (what the reference takes from its simulator's renderer, src/sim/sim_env/flex_env.py:151-189, :404-409): depth and
+ * id images of E particle scenes from C calibrated pinhole cameras in ONE launch, every particle a sphere, the table a plane.  No tool, no colour,
+ * no sensor noise.  The arithmetic is stated by adaptigraph_amd/render.py:render_depth_host and repeated here operation for
+ * operation -- float64 on float32 inputs, products and sums rounded separately, only + - * / sqrt -- so the kernel gives the statement's bits.
+ * DEVICE arrays: pts (E,n_max,3) fp32 sphere centres in the cameras' world frame; n (E) int32 spheres per episode (an n outside 0 .. n_max renders
+ * as 0; rows >= n are never read); radius (E) fp32; cams (C,25) doubles = Kinv (3x3 row-major, the inverse intrinsics computed by the caller),
+ * R (3x3), t (3) with p_world = R p_cam + t as ag_depth_cloud reads them, then fx, fy, cx, cy of the pinhole (zero skew; they only bound a
+ * sphere's pixels); plane (4) doubles (nx, ny, nz, o), the table nx x + ny y + nz z = o in the world frame, or NULL for none; limits (2) doubles =
+ * near, far with 0 <= near < far.
+ * Sphere i in camera c: d = float64(p) - t, c_r = (R[0,r] d_0 + R[1,r] d_1) + R[2,r] d_2, rr = float64(radius); it takes part iff c_2 - rr > near.
+ * Pixel (u, v): qx = (Kinv[0,0] u + Kinv[0,1] v) + Kinv[0,2], qy from row 1, A = (qx qx + qy qy) + 1, B = (qx c_0 + qy c_1) + c_2,
+ * Cc = ((c_0 c_0 + c_1 c_1) + c_2 c_2) - rr rr, disc = B B - A Cc; a hit iff disc >= 0, at d = (B - sqrt(disc)) / A, counted iff near < d < far.
+ * Plane: w_r = (R[r,0] qx + R[r,1] qy) + R[r,2], den = (nx w_0 + ny w_1) + nz w_2, num = o - ((nx t_0 + ny t_1) + nz t_2); den != 0: dp = num / den,
+ * counted iff near < dp < far.  The smallest double wins: spheres in ascending index with strict <, the plane only if strictly smaller than
+ * every sphere hit.  Out: depth (E,C,H,W) fp32 = float(winner), 0 where nothing counts; id (E,C,H,W) int32 = the particle, -1 the plane, -2 nothing.
+ * One 256-thread workgroup per (episode, camera, AG_RENDER_TILE x AG_RENDER_TILE pixels), the particles staged through LDS in chunks of
+ * AG_RENDER_CHUNK and compacted in index order; every pixel written once.
+ * AG_ERR_ARG, nothing launched: a null pts / n / radius / cams / limits / depth / id, E or C < 1, H or W outside 1 .. AG_RENDER_MAX_SIDE, n_max
+ * outside 1 .. AG_RENDER_MAX_PARTICLES.  No host synchronisation, no atomics, the same bits on every call: safe to capture. */
+#define AG_RENDER_TILE 32
+#define AG_RENDER_CHUNK 256
+#define AG_RENDER_MAX_SIDE 4096
+#define AG_RENDER_MAX_PARTICLES 4096
+int ag_render_depth(const float *pts, const int32_t *n, const float *radius, const double *cams, const double *plane, const double *limits, int E,
+                    int n_max, int C, int H, int W, float *depth, int32_t *id, ag_stream_t stream);
+
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
  *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
