@@ -140,6 +140,8 @@ SIGNATURES = {
     "ag_sim_pile_push": (c_int, [c_void_p] * 11 + [c_int] * 8 + [c_float] * 9 + [c_void_p]),
     # cloth grasp-and-drag simulator
     "ag_sim_cloth_push": (c_int, [c_void_p] * 14 + [c_int] * 8 + [c_float] * 8 + [c_void_p]),
+    # box push simulator
+    "ag_sim_box_push": (c_int, [c_void_p] * 13 + [c_int] * 8 + [c_float] * 9 + [c_void_p]),
     # simulated depth cameras
     "ag_render_depth": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 3),
     # training batches assembled on the device

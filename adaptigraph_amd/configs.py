@@ -20,8 +20,16 @@ def model_config():
     return copy.deepcopy(MODEL_CONFIG)
 
 
+_BOX_PARAMS = ("com_x", "com_y")      # the box's TWO used parameters: the centre of mass as a fraction of each side, from the corner
+
+
 def material_config(material):
-    """material_config with exactly one used physics parameter (rope.yaml:109-112, granular.yaml:101-104)."""
+    """material_config with exactly one used physics parameter (rope.yaml:109-112, granular.yaml:101-104); the box has two (the reference
+    ships no dynamics config for it: the names are those of datagen's property_params.pkl)."""
+    if material == "box":
+        return {"material_index": {material: 0},
+                material: {"physics_params": [{"name": "particle_radius", "use": False, "min": 0.0, "max": 1.0}]
+                           + [{"name": name, "use": True, "min": 0.0, "max": 1.0} for name in _BOX_PARAMS]}}
     return {"material_index": {material: 0},
             material: {"physics_params": [{"name": "particle_radius", "use": False, "min": 0.0, "max": 1.0},
                                           {"name": _USED_PARAM[material], "use": True, "min": 0.0, "max": 1.0}]}}
@@ -49,6 +57,16 @@ TASK_CONFIG = {   # config/planning/{rope,granular,cloth}.yaml
                   adj_thresh=0.75, fps_radius=0.30, eef_num=1, topk=5, connect_tools_all=True, push_length=0.1,
                   pusher_points=[[0.0, 0.0, 0.170]], gripper_enable=True,
                   action_lower_lim=[-4.5, -2.5, -3.14, 2], action_upper_lim=[0.0, 4.5, 3.14, 10]),
+    # The reference ships no planning config for the box; these are chosen for this project's box model (sim.py, one unit = 100 px of box.yaml).
+    #   fps_radius 0.20: 2.5 particle spacings (2 r = 0.08): the largest box (3.0 x 2.0) keeps 15 x 10 = 150 key points, under max_nobj without its cap, the smallest (1.5 x 0.5) 8 x 3
+    #   adj_thresh 0.50: 2.5 fps_radius, the rope's ratio: a key point reaches its neighbours two rings out, and the pusher (R 0.1) the face it touches
+    #   topk 10: the rope's; of the 12 key points two rings out on a square lattice, the nearest ten
+    #   action limits: starts anywhere in the +-4.5 x +-4.5 of the other materials' workspace and angles all round, so a push can start on ANY
+    #   side of the box (the other materials' x <= 0 would only ever reach one), 5 .. 15 steps of push_length 0.1
+    "box": dict(_TASK_COMMON, material="box", material_indices={"box": 0}, material_dims={"box": 2},
+                adj_thresh=0.50, fps_radius=0.20, eef_num=1, topk=10, connect_tools_all=False, push_length=0.1,
+                pusher_points=[[0.0, 0.0, 0.12]], gripper_enable=False,
+                action_lower_lim=[-4.5, -4.5, -3.14, 5], action_upper_lim=[4.5, 4.5, 3.14, 15]),
 }
 
 

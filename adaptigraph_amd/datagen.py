@@ -1,9 +1,10 @@
-"""Rope, granular and cloth datasets from the particle simulators (sim.py), written in the layout `load.py` reads — the work of the reference's
+"""Rope, granular, cloth and box datasets from the particle simulators (sim.py), written in the layout `load.py` reads — the work of the reference's
 src/sim/data_gen/data_gen.py followed by src/dynamics/preprocess/preprocess.py:135-230, without the .h5 files in between.
 
     python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5                          # rope
     python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5 --material granular
     python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5 --material cloth
+    python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5 --material box
 
     DIR/sim_data/rope/<episode:06>/property_params.pkl          {'particle_radius', 'stiffness'}
     DIR/preprocess/rope/frame_pairs/<episode:06>_<push:02>.txt  rows of n_his + n_future frame indices (preprocess.extract_push)
@@ -15,7 +16,11 @@ With --material granular the same tree under .../granular/: property_params.pkl 
 eef_pos entries are (T, 5, 3) (the board's five key points), obj_pos entries (T, n_e, 3) with n_e grains in episode e, phys_range.txt the
 range of granular_scale.  With --material cloth the tree under .../cloth/: property_params.pkl holds {'particle_radius', 'sf',
 'stretch_stiffness', 'bend_stiffness', 'shear_stiffness', 'dynamic_friction'}, eef_pos entries are (T, 2, 3) (the gripper's two finger points),
-obj_pos entries (T, nx_e nz_e, 3), phys_range.txt the range of sf.
+obj_pos entries (T, nx_e nz_e, 3), phys_range.txt the range of sf.  With --material box the tree under .../box/: property_params.pkl holds
+{'particle_radius', 'box_width', 'box_height', 'com_x', 'com_y'} -- com_x, com_y the TWO physics parameters, the centre of mass as a fraction of
+the side from the box's corner, in [0.1, 0.9] --, eef_pos entries are (T, 1, 3), obj_pos entries (T, nx_e nz_e, 3), phys_range.txt two columns,
+and every episode directory also gets what data_gen_box.py:98-105 writes: box_states.npy (T, 3: x, z, theta of the centre of mass),
+eef_states.npy (T, 2: the pusher's x, z) and box_com.npy ([[a, b], [com.x, com.z]], the centre of mass in units from the geometric centre).
 """
 import argparse
 import os
@@ -60,8 +65,19 @@ def default_cloth_dataset_config():
     return dict(configs.dataset_config("cloth"), dist_thresh=CLOTH_DIST_THRESH)
 
 
+# A box push (speed 0.01, a frame every 10 steps) is 5.0 long and takes 500 or 501 steps (the float32 end points decide), so a frame is 0.0998
+# or 0.1 of travel: the spacing data_gen_box.py:67-74 moves its pusher per frame.  A threshold AT 0.1 would skip every other frame whenever the
+# spacing rounds below it, as for the rope; the default sits just under the spacing, so tuples step by one frame.
+BOX_DIST_THRESH = 0.095
+
+
+def default_box_dataset_config():
+    return dict(configs.dataset_config("box"), dist_thresh=BOX_DIST_THRESH)
+
+
 def _write_dataset(root, ds, properties, phys, pairs, eef_pos, obj_pos):
-    """The files of one dataset: properties (one dict per episode), phys (E) the physics parameter, pairs {(e, k): rows}, positions per episode."""
+    """The files of one dataset: properties (one dict per episode), phys (E) the physics parameter or (E, d) the d of them, pairs {(e, k): rows},
+    positions per episode."""
     name = ds["data_name"]
     data_dir, prep_dir = os.path.join(root, "sim_data"), os.path.join(root, "preprocess")
     pairs_dir = os.path.join(prep_dir, name, "frame_pairs")
@@ -74,7 +90,8 @@ def _write_dataset(root, ds, properties, phys, pairs, eef_pos, obj_pos):
             pickle.dump(prop, f)
     with open(os.path.join(prep_dir, name, "positions.pkl"), "wb") as f:
         pickle.dump({"eef_pos": [np.concatenate(p) for p in eef_pos], "obj_pos": [np.concatenate(p) for p in obj_pos]}, f)
-    phys = np.asarray(phys).astype(np.float32)[:, None]
+    phys = np.asarray(phys).astype(np.float32)
+    phys = phys[:, None] if phys.ndim == 1 else phys
     np.savetxt(os.path.join(prep_dir, name, "phys_range.txt"), np.stack([phys.min(0), phys.max(0)]))
     with open(os.path.join(prep_dir, name, "metadata.txt"), "w") as f:
         f.write(f"{ds['dist_thresh']},{ds['n_future']},{ds['n_his']}")
@@ -148,6 +165,47 @@ def generate_cloth_dataset(root, n_episodes, n_pushes, seed=0, device=None, data
     return _write_dataset(root, ds, properties, sf, pairs, eef_pos, obj_pos)
 
 
+def generate_box_dataset(root, n_episodes, n_pushes, seed=0, device=None, dataset_config=None, params=sim.BOX_DEFAULT, push_length=5.0):
+    """Simulate n_episodes boxes through n_pushes pushes each and write the dataset under `root`.  Episode e draws its box (`sim.initial_box`: its
+    sides, its centre of mass, its angle) and its pushes (`sim.sample_box_push`, `push_length` long, in the box's frame as it lies) from
+    numpy.random.default_rng(seed + e); push k of ALL episodes, whatever their grids, is one `sim.box_push` call on `device`, read back once.
+    device=None runs the host statement `sim.box_push_host` instead: the same files with the same bytes.
+    -> dataset_config with data_dir / prep_data_dir filled in."""
+    ds = dict(default_box_dataset_config() if dataset_config is None else dataset_config)
+    rngs = [np.random.default_rng(seed + e) for e in range(n_episodes)]
+    sizes, coms, angles = zip(*(sim.initial_box(rng) for rng in rngs))
+    scene = sim.BoxScene.from_boxes(sizes, coms, angles, r=params.r)
+    eef_pos, obj_pos, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes, {}
+    states = [[] for _ in rngs]
+    for k in range(n_pushes):
+        push = np.stack([sim.sample_box_push(scene.row(e), rngs[e], push_length) for e in range(n_episodes)])
+        if device is None:
+            obj, eef, poses, nf, pose, vel = sim.box_push_host(scene, push, params)
+        else:
+            obj, eef, poses, nf, pose, vel = (t.cpu().numpy() for t in sim.box_push(scene, push, params, device=device))
+        scene.pose, scene.vel = pose, vel
+        scene.x = sim.box_particles(pose, scene.q, scene.n, params.r)
+        for e in range(n_episodes):
+            tool = eef[e, :nf[e], None, :]
+            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
+            n_frames[e] += cnt
+            eef_pos[e].append(tool)
+            obj_pos[e].append(obj[e, :nf[e], :scene.n[e]])
+            p = poses[e, :nf[e]].astype(np.float64)
+            states[e].append(np.stack([p[:, 0], p[:, 1], np.arctan2(p[:, 3], p[:, 2])], 1))
+    properties = [{"particle_radius": float(params.r), "box_width": float(scene.size[e, 0]), "box_height": float(scene.size[e, 1]),
+                   "com_x": float(scene.com[e, 0]) + 0.5, "com_y": float(scene.com[e, 1]) + 0.5} for e in range(n_episodes)]
+    phys = np.array([[p["com_x"], p["com_y"]] for p in properties])
+    out = _write_dataset(root, ds, properties, phys, pairs, eef_pos, obj_pos)
+    for e in range(n_episodes):
+        epi = os.path.join(out["data_dir"], ds["data_name"], f"{e:06}")
+        np.save(os.path.join(epi, "box_states.npy"), np.concatenate(states[e]))
+        np.save(os.path.join(epi, "eef_states.npy"), np.concatenate(eef_pos[e])[:, 0, [0, 2]].astype(np.float64))
+        size = scene.size[e].astype(np.float64)
+        np.save(os.path.join(epi, "box_com.npy"), np.stack([size, scene.com[e].astype(np.float64) * size]))
+    return out
+
+
 def generate_rope_dataset(root, n_episodes, n_pushes, seed=0, device=None, dataset_config=None, n_particles=128, params=sim.DEFAULT):
     """Simulate n_episodes ropes of n_particles particles through n_pushes pushes each and write the dataset under `root`.  Episode e draws its
     rope, its stiffness and its pushes from numpy.random.default_rng(seed + e) (data_gen.py:27 seeds per episode); push k of ALL episodes is one
@@ -181,7 +239,7 @@ def main(argv=None):
     ap.add_argument("--out", required=True, help="dataset root")
     ap.add_argument("--episodes", type=int, default=64)
     ap.add_argument("--pushes", type=int, default=5)
-    ap.add_argument("--material", choices=("rope", "granular", "cloth"), default="rope")
+    ap.add_argument("--material", choices=("rope", "granular", "cloth", "box"), default="rope")
     ap.add_argument("--particles", type=int, default=128, help="rope only; a pile's number of grains follows from its scene")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0", help="a GPU, or 'host' for the numpy restatement (slow)")
@@ -194,6 +252,10 @@ def main(argv=None):
     if args.material == "cloth":
         ds = generate_cloth_dataset(args.out, args.episodes, args.pushes, args.seed, device)
         print(f"{args.episodes} episodes x {args.pushes} grasp-and-drags of cloths under {ds['data_dir']} and {ds['prep_data_dir']}")
+        return
+    if args.material == "box":
+        ds = generate_box_dataset(args.out, args.episodes, args.pushes, args.seed, device)
+        print(f"{args.episodes} episodes x {args.pushes} pushes of boxes under {ds['data_dir']} and {ds['prep_data_dir']}")
         return
     ds = generate_rope_dataset(args.out, args.episodes, args.pushes, args.seed, device, n_particles=args.particles)
     print(f"{args.episodes} episodes x {args.pushes} pushes of {args.particles} particles under {ds['data_dir']} and {ds['prep_data_dir']}")

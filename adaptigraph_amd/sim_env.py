@@ -23,7 +23,7 @@ import numpy as np
 
 from . import perception, render, sim
 
-MATERIALS = ("rope", "granular", "cloth")
+MATERIALS = ("rope", "granular", "cloth", "box")
 DEFAULT_BBOX = ((-0.7, 0.7), (-0.7, 0.7), (-0.5, 0.05))      # board frame, metres: the work area and everything above the table (z is down)
 
 
@@ -44,8 +44,8 @@ def to_board_frame(points, sim_real_ratio):
 
 
 class SimEnv:
-    """SimEnv(material, scene, task_config, cameras=None, device="cuda:0", params=None): `material` "rope" / "granular" / "cloth"; `scene` a
-    RopeScene / PileScene / ClothScene with E = 1 (copied; `env.scene` is the current one, host arrays, or device tensors in x, v on the device
+    """SimEnv(material, scene, task_config, cameras=None, device="cuda:0", params=None): `material` "rope" / "granular" / "cloth" / "box"; `scene` a
+    RopeScene / PileScene / ClothScene / BoxScene with E = 1 (copied; `env.scene` is the current one, host arrays, or device tensors in x, v on the device
     path); `task_config` gives sim_real_ratio and push_length; `cameras` = (R_list, t_list, intr_list) in the board frame (default:
     render.default_cameras); `params` the simulator's parameters (default: the material's).  Keyword-only: `image_size` (H, W) of the cameras,
     `stride` of the perception, `bbox` (3, 2) the board-frame crop box, `near`, `far` the depth range in metres."""
@@ -58,7 +58,8 @@ class SimEnv:
             raise ValueError("SimEnv: one episode per environment (E = 1)")
         self.material, self.task_config = material, task_config
         self.ratio = float(task_config["sim_real_ratio"])
-        self.params = params if params is not None else {"rope": sim.DEFAULT, "granular": sim.PILE_DEFAULT, "cloth": sim.CLOTH_DEFAULT}[material]
+        self.params = params if params is not None else {"rope": sim.DEFAULT, "granular": sim.PILE_DEFAULT, "cloth": sim.CLOTH_DEFAULT,
+                                                              "box": sim.BOX_DEFAULT}[material]
         self.H, self.W = int(image_size[0]), int(image_size[1])
         self.stride, self.near, self.far = int(stride), float(near), float(far)
         self.R_list, self.t_list, self.intr_list = cameras if cameras is not None else render.default_cameras(self.ratio, self.H, self.W)
@@ -70,14 +71,16 @@ class SimEnv:
         self.n = np.asarray(scene.n, np.int32).reshape(1)
         self.device = None
         x, v = np.array(scene.x, np.float32), np.array(scene.v, np.float32)
+        pose = np.array(scene.pose, np.float32) if material == "box" else None
         if device is not None:
             import torch
             self.device = torch.device(device)
             x, v = torch.from_numpy(x).to(self.device), torch.from_numpy(v).to(self.device)
+            pose = torch.from_numpy(pose).to(self.device) if material == "box" else None
             self._renderer = render.DeviceRenderer(self.R_list, self.t_list, self.intr_list, self.H, self.W, self.plane, self.near, self.far, 1,
                                                    self.device)
             self._n_dev, self._radius_dev = torch.from_numpy(self.n).to(self.device), torch.from_numpy(self.radius).to(self.device)
-        self.scene = dataclasses.replace(scene, x=x, v=v)
+        self.scene = dataclasses.replace(scene, x=x, pose=pose, vel=v) if material == "box" else dataclasses.replace(scene, x=x, v=v)
 
     # ---- RealEnv's observation surface
     def render(self):
@@ -127,6 +130,8 @@ class SimEnv:
     # ---- RealEnv's action surface
     def _push(self, segment):
         push = np.asarray(segment, np.float64).astype(np.float32).reshape(1, 4)
+        if self.material == "box":
+            return self._push_box(push)
         if self.device is None:
             host = {"rope": sim.rope_push_host, "granular": sim.pile_push_host, "cloth": sim.cloth_push_host}[self.material]
             x, v = host(self.scene, push, self.params)[-2:]
@@ -144,12 +149,27 @@ class SimEnv:
         self.scene = dataclasses.replace(self.scene, x=x, v=v)
         return push[0]
 
+    def _push_box(self, push):
+        """The box keeps its pose and velocity (on the device, on the device path); x, what the cameras see, is the last frame of the push:
+        frame frames_of(n_push) - 1, a number the host knows without reading anything back."""
+        if self.device is None:
+            obj, _, _, n_frames, pose, vel = sim.box_push_host(self.scene, push, self.params)
+        else:
+            call = sim.DeviceBoxPush(self.scene, push, self.params, device=self.device)
+            sim._box_validate(self.scene, call.steps, call.dims[2], self.params)
+            obj, _, _, _, pose, vel = call.launch()
+            n_frames = sim.frames_of(call.steps, self.params)
+        self.scene = dataclasses.replace(self.scene, x=obj[:, int(n_frames[0]) - 1], pose=pose, vel=vel)
+        return push[0]
+
     def step(self, action, decoded=False):
         """real_env.py:212-240: one push from the action's start to its end.  -> the (xs, zs, xe, ze) float32 that was simulated."""
         return self._push(action if decoded else decode_action(action, self.task_config["push_length"]))
 
     def step_gripper(self, action, decoded=False):
         """real_env.py:242-276: one grasp-and-drag; the start moves back by 5 mm along the drag as lines 262-263 compute it."""
+        if self.material == "box":
+            raise ValueError("SimEnv: a box is pushed, not grasped (step_gripper is for the cloth)")
         x_start, z_start, x_end, z_end = action if decoded else decode_action(action, self.task_config["push_length"])
         back = 0.005 * self.ratio
         x_start = x_start - back * (x_end - x_start) / np.sqrt((x_end - x_start) ** 2 + (z_end - z_start) ** 2)

@@ -582,6 +582,34 @@ int ag_sim_cloth_push(const int32_t *nx, const int32_t *nz, const float *rest, c
                       int E, int n_max, int F_max, int n_push_max, int substeps, int iters, int record_every, int settle, float h, float g,
                       float r, float damp, float lift, float grasp2, float finger, float tool_y, ag_stream_t stream);
 
+/* ---- box push simulator (the data side for the box material; stands in for src/sim/data_gen/data_gen_box.py over the 2-D rigid-body engine of
+ * src/sim/sim_env/pymunk_env.py): ONE push of E rigid-box episodes in one launch, one 256-thread workgroup per episode, up to four particles
+ * per thread.  The model is this project's own (NOT pymunk), stated operation for operation by
+ * adaptigraph_amd/sim.py:box_push_host; the kernel gives the same bits.  A box is a rigid rectangle whose centre of mass is off its geometric
+ * centre, sampled by n particles.  Per-episode DEVICE arrays: n (E) particles (4 .. n_max); q (E,n_max,2) their rest coordinates relative to
+ * the centre of mass and m (E,n_max) their masses (0 <= m <= 1, sum 1), rows >= n never read; body (E,6) = the footprint x_lo, x_hi, z_lo,
+ * z_hi relative to the centre of mass, the inertia I = sum m |q|^2 (> 0), rho_max >= max |q| (0 < rho_max <= 8); n_push steps of the push
+ * (1 .. n_push_max), inv = float(1 / (n_push substeps)); push (E,4) = xs, zs, xe, ze.  State pose (E,4) = X, Z, co, si of the centre of mass
+ * ((co, si) a unit vector) and vel (E,3) = VX, VZ, Omega, read and written in place.
+ * Per step `substeps` substeps of h seconds: predict (the rotation in Cayley form, renormalised); `iters` rigid positional corrections against
+ * the frictionless cylindrical pusher of radius R (push steps only; a pusher centre inside the footprint leaves through the nearest face; the
+ * part of a penetration beyond `cap` moves the box and the pose the substep started from alike, so that no velocity comes of it);
+ * velocities from the change of pose; Coulomb friction mu under gravity g of every particle on the table, implicit: k_i = m_i mu g /
+ * max(|u_i|, eps), four sums over the particles (integers scaled by 2^22, exact in any order) and a 3 x 3 solve; at rest (exactly zero) once
+ * |V| + |Omega| rho_max < v_rest.  After the n_push steps `settle` steps without the pusher.
+ * Out: obj (E,F_max,n_max,3), eef (E,F_max,3) and pose_frames (E,F_max,4): frame f holds the particles (X + Rot q at height r), the pusher
+ * point (c.x, r, c.z) and the pose after push step f record_every; the episode's last frame those after the settle with the pusher point
+ * (xe, r + lift, ze); n_frames (E) = (n_push - 1) / record_every + 2, rows and frames behind untouched.
+ * AG_ERR_ARG, nothing launched: a null pointer, n_max outside 4 .. AG_SIM_BOX_MAX_PARTICLES, F_max < (n_push_max - 1) / record_every + 2,
+ * substeps, iters or record_every < 1, (mu g) / eps outside (0, 8192] (with rho_max <= 8 the bound under which the integer sums stay inside
+ * 2^51).  n_max and n_push_max are the host's bounds on the device arrays: an episode whose n, n_push, inertia or rho_max lies outside the
+ * bounds writes n_frames = 0 and nothing else.  No host synchronisation, no atomics, the same bits on every call: safe to capture. */
+#define AG_SIM_BOX_MAX_PARTICLES 1024
+int ag_sim_box_push(const int32_t *n, const float *q, const float *m, const float *body, const float *inv, const int32_t *n_push,
+                    const float *push, float *pose, float *vel, float *obj, float *eef, float *pose_frames, int32_t *n_frames, int E, int n_max,
+                    int F_max, int n_push_max, int substeps, int iters, int record_every, int settle, float h, float g, float mu, float r, float R,
+                    float eps, float v_rest, float cap, float lift, ag_stream_t stream);
+
 /* ---- simulated depth cameras (what the reference takes from its simulator's renderer, src/sim/sim_env/flex_env.py:151-189, :404-409): depth and
  * id images of E particle scenes from C calibrated pinhole cameras in ONE launch, every particle a sphere, the table a plane.  No tool, no colour,
  * no sensor noise.  The arithmetic is stated by adaptigraph_amd/render.py:render_depth_host and repeated here operation for
