@@ -57,7 +57,7 @@ TASK_CONFIG = {   # config/planning/{rope,granular,cloth}.yaml
                   adj_thresh=0.75, fps_radius=0.30, eef_num=1, topk=5, connect_tools_all=True, push_length=0.1,
                   pusher_points=[[0.0, 0.0, 0.170]], gripper_enable=True,
                   action_lower_lim=[-4.5, -2.5, -3.14, 2], action_upper_lim=[0.0, 4.5, 3.14, 10]),
-    # The reference ships no planning config for the box; these are chosen for this project's box model (sim.py, one unit = 100 px of box.yaml).
+    # The reference ships no planning config for the box; these are chosen for this project's box model (sim/box.py, one unit = 100 px of box.yaml).
     #   fps_radius 0.20: 2.5 particle spacings (2 r = 0.08): the largest box (3.0 x 2.0) keeps 15 x 10 = 150 key points, under max_nobj without its cap, the smallest (1.5 x 0.5) 8 x 3
     #   adj_thresh 0.50: 2.5 fps_radius, the rope's ratio: a key point reaches its neighbours two rings out, and the pusher (R 0.1) the face it touches
     #   topk 10: the rope's; of the 12 key points two rings out on a square lattice, the nearest ten

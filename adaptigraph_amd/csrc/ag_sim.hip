@@ -1,6 +1,6 @@
 // ag_sim.hip — a batched rope-on-table particle simulator: one push of E episodes in one launch.  It stands in for the data side of the
 // reference (src/sim/sim_env/flex_env.py:258-402 steps a closed CUDA solver); the model is this project's own, stated operation for operation in
-// adaptigraph_amd/sim.py (rope_push_host, the float32 numpy restatement) and repeated here so that both give the same bits.
+// adaptigraph_amd/sim/rope.py (rope_push_host, the float32 numpy restatement) and repeated here so that both give the same bits.
 //
 // One 256-thread workgroup owns an episode for the whole push, one particle per thread (n <= 256).  Positions and the cluster fits live in LDS (seven
 // planes of 256 floats = 7 KB), the particle's own position, start-of-substep position and velocity in registers.  A substep:
@@ -14,7 +14,7 @@
 // rewritten behind barriers 1-3 of the next substep.  Whether an episode has clusters, pushes or records is uniform over its workgroup, so every
 // barrier is reached by all 256 threads.  No atomics; every float sum runs in the stated order (no butterfly reductions), every product is rounded
 // on its own (-ffp-contract=off), division and square root are the correctly rounded ones.
-#include "ag_host.h"
+#include "ag_sim_dev.h"
 
 namespace {
 
@@ -47,10 +47,7 @@ __global__ __launch_bounds__(kRopeThreads) void rope_push_kernel(const RopePushA
     __shared__ float s_cx[kRopeThreads], s_cz[kRopeThreads], s_ux[kRopeThreads], s_uz[kRopeThreads];
     const int e = blockIdx.x, i = threadIdx.x;
     const int n = a.n[e], n_push = a.n_push[e];
-    if (n < 2 || n > a.n_max || n_push < 1 || n_push > a.n_push_max) {      // (uniform) an episode the host's checks could not see: no frame, nothing touched
-        if (i == 0) a.n_frames[e] = 0;
-        return;
-    }
+    if (n < 2 || n > a.n_max || n_push < 1 || n_push > a.n_push_max) return sim_no_frame(a.n_frames, e, i);
     const bool live = i < n;
     const size_t row = ((size_t)e * a.n_max + (live ? i : 0)) * 3;
     float x = live ? a.x[row] : 0.f, y = live ? a.x[row + 1] : 0.f, z = live ? a.x[row + 2] : 0.f;
@@ -112,8 +109,7 @@ __global__ __launch_bounds__(kRopeThreads) void rope_push_kernel(const RopePushA
             }
             // d. pusher
             if (pushing) {
-                const float t = (float)(st * S + s + 1) * inv;
-                cx = sx + (ex - sx) * t; cz = sz + (ez - sz) * t;
+                sim_tool_centre(cx, cz, sx, sz, ex, ez, sim_substep_t(st, S, s, inv));
                 const float dx = px - cx, dz = pz - cz;
                 const float d = sqrtf(dx * dx + dz * dz);
                 if (d > 0.f && d < reach) {
@@ -127,36 +123,28 @@ __global__ __launch_bounds__(kRopeThreads) void rope_push_kernel(const RopePushA
             // f. velocity and friction
             vx = (px - x) / h; vy = (py - y) / h; vz = (pz - z) / h;
             if (on) {
-                const float sp = sqrtf(vx * vx + vz * vz);
-                const float f = sp > mgh ? 1.f - mgh / sp : 0.f;
+                const float f = sim_coulomb(vx, vz, mgh);
                 vx = vx * f; vz = vz * f;
             }
             x = px; y = py; z = pz;
         }
         if (pushing && st % a.record_every == 0) {
-            const int f = st / a.record_every;                               // < F_max: checked on the host against n_push_max
-            if (live) {
-                float *o = frames + ((size_t)f * a.n_max + i) * 3;
-                o[0] = x; o[1] = y; o[2] = z;
-            }
-            if (i == 0) { tool[3 * f] = cx; tool[3 * f + 1] = r; tool[3 * f + 2] = cz; }
+            const int f = sim_recorded_frame(st, a.record_every);
+            if (live) sim_store3(frames + ((size_t)f * a.n_max + i) * 3, x, y, z);
+            if (i == 0) sim_store3(tool + 3 * f, cx, r, cz);
         }
     }
-    const int f = (n_push - 1) / a.record_every + 1;
+    const int f = sim_final_frame(n_push, a.record_every);
     if (live) {
-        float *o = frames + ((size_t)f * a.n_max + i) * 3;
-        o[0] = x; o[1] = y; o[2] = z;
-        a.x[row] = x; a.x[row + 1] = y; a.x[row + 2] = z;
-        a.v[row] = vx; a.v[row + 1] = vy; a.v[row + 2] = vz;
+        sim_store3(frames + ((size_t)f * a.n_max + i) * 3, x, y, z);
+        sim_store3(a.x + row, x, y, z);
+        sim_store3(a.v + row, vx, vy, vz);
     }
     if (i == 0) {
-        tool[3 * f] = ex; tool[3 * f + 1] = r + a.lift; tool[3 * f + 2] = ez;
+        sim_store3(tool + 3 * f, ex, r + a.lift, ez);
         a.n_frames[e] = f + 1;
     }
 }
-
-// frames a push of n_push steps writes: steps 0, record_every, 2 record_every ... < n_push, and the one after the settle
-int rope_frames(int n_push, int record_every) { return (n_push - 1) / record_every + 2; }
 
 }  // namespace
 
@@ -169,16 +157,9 @@ int ag_sim_rope_push(const int32_t *n, const float *l0, const int32_t *w, const 
 {
     if (!n || !l0 || !w || !kappa || !inv || !n_push || !push || !x || !v || !obj || !eef || !n_frames)
         return ag_fail(AG_ERR_ARG, "ag_sim_rope_push: null argument");
-    if (E < 1) return ag_fail(AG_ERR_ARG, "ag_sim_rope_push: E = %d episodes", E);
-    if (n_max < 2 || n_max > AG_SIM_ROPE_MAX_PARTICLES)
-        return ag_fail(AG_ERR_ARG, "ag_sim_rope_push: n_max = %d outside 2 .. %d (AG_SIM_ROPE_MAX_PARTICLES)", n_max, AG_SIM_ROPE_MAX_PARTICLES);
-    if (n_push_max < 1 || substeps < 1 || record_every < 1 || settle < 0 || n_push_max > INT32_MAX / substeps - settle - 1)
-        return ag_fail(AG_ERR_ARG, "ag_sim_rope_push: n_push_max = %d substeps = %d record_every = %d settle = %d", n_push_max, substeps,
-                       record_every, settle);
-    if (F_max < rope_frames(n_push_max, record_every))
-        return ag_fail(AG_ERR_ARG, "ag_sim_rope_push: F_max = %d frames, a push of %d steps recorded every %d writes %d", F_max, n_push_max,
-                       record_every, rope_frames(n_push_max, record_every));
-    if (!(h > 0.f)) return ag_fail(AG_ERR_ARG, "ag_sim_rope_push: substep h = %g", (double)h);
+    if (int err = sim_check_schedule("ag_sim_rope_push", E, n_max, 2, AG_SIM_ROPE_MAX_PARTICLES, "AG_SIM_ROPE_MAX_PARTICLES", F_max, n_push_max, 1,
+                                     substeps, false, 0, record_every, settle, h, "push"))
+        return err;
     RopePushArgs a{n, w, n_push, l0, kappa, inv, push, x, v, obj, eef, n_frames, n_max, F_max, n_push_max, substeps, record_every, settle,
                    h, g, r, R, mu, lift};
     hipLaunchKernelGGL(rope_push_kernel, dim3(E), dim3(kRopeThreads), 0, static_cast<hipStream_t>(stream), a);

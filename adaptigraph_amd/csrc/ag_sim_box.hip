@@ -1,6 +1,6 @@
 // ag_sim_box.hip — a batched rigid-box-on-table simulator: one push of E box episodes in one launch.  It stands in for the data side of the
 // reference's fourth material (src/sim/data_gen/data_gen_box.py over src/sim/sim_env/pymunk_env.py, a 2-D rigid-body engine that does not
-// exist here); the model is this project's own (not pymunk, not fitted to it), stated operation for operation in adaptigraph_amd/sim.py
+// exist here); the model is this project's own (not pymunk, not fitted to it), stated operation for operation in adaptigraph_amd/sim/box.py
 // (box_push_host, the float32 numpy statement) and repeated here so that both give the same bits.
 //
 // One 256-thread workgroup owns an episode for the whole call.  The body's state -- pose (X, Z, co, si), velocity (VX, VZ, Omega) -- is seven
@@ -15,14 +15,14 @@
 // of buffer p.  n, the step counts, pushing and recording are uniform over a workgroup, and an episode outside its bounds returns as a whole
 // before the first barrier.  No atomics, no float reductions.  Every product is rounded on its own (-ffp-contract=off), division and square
 // root are the correctly rounded ones.
-#include "ag_host.h"
+#include "ag_sim_dev.h"
 #include "ag_block_dev.h"
 
 namespace {
 
 constexpr int kBoxThreads = 256;
 constexpr int kBoxPer = AG_SIM_BOX_MAX_PARTICLES / kBoxThreads;      // particles per thread
-constexpr float kBoxRhoMax = 8.f, kBoxKMax = 8192.f;                 // sim.py: BOX_RHO_MAX, BOX_K_MAX
+constexpr float kBoxRhoMax = 8.f, kBoxKMax = 8192.f;                 // sim/box.py: BOX_RHO_MAX, BOX_K_MAX
 constexpr float kQ22 = 4194304.f;
 
 struct BoxPushArgs {
@@ -54,10 +54,8 @@ __global__ __launch_bounds__(kBoxThreads) void box_push_kernel(const BoxPushArgs
     const int n = a.n[e], n_push = a.n_push[e];
     const float *body = a.body + 6 * e;
     const float xlo = body[0], xhi = body[1], zlo = body[2], zhi = body[3], I = body[4], rho_max = body[5];
-    if (n < 4 || n > a.n_max || n_push < 1 || n_push > a.n_push_max || !(I > 0.f) || !(rho_max > 0.f) || rho_max > kBoxRhoMax) {
-        if (t == 0) a.n_frames[e] = 0;      // (uniform) no frame, nothing touched
-        return;
-    }
+    if (n < 4 || n > a.n_max || n_push < 1 || n_push > a.n_push_max || !(I > 0.f) || !(rho_max > 0.f) || rho_max > kBoxRhoMax)
+        return sim_no_frame(a.n_frames, e, t);
     const float inv = a.inv[e];
     const float xs = a.push[4 * e], zs = a.push[4 * e + 1], xe = a.push[4 * e + 2], ze = a.push[4 * e + 3];
     const float h = a.h, r = a.r, R = a.R, eps = a.eps, cap = a.cap, mug = a.mu * a.g;
@@ -88,8 +86,7 @@ __global__ __launch_bounds__(kBoxThreads) void box_push_kernel(const BoxPushArgs
             box_turn(co, si, (Om * h) * 0.5f);
             // b. pusher
             if (pushing) {
-                const float tt = (float)(st * S + s + 1) * inv;
-                cx = xs + (xe - xs) * tt; cz = zs + (ze - zs) * tt;
+                sim_tool_centre(cx, cz, xs, zs, xe, ze, sim_substep_t(st, S, s, inv));
                 for (int it = 0; it < a.iters; ++it) {
                     const float dx = cx - X, dz = cz - Z;
                     const float lx = co * dx + si * dz, lz = co * dz - si * dx;
@@ -156,36 +153,30 @@ __global__ __launch_bounds__(kBoxThreads) void box_push_kernel(const BoxPushArgs
             VX = wx; VZ = wz; Om = wo;
         }
         if (pushing && st % a.record_every == 0) {
-            const int f = st / a.record_every;                               // < F_max: checked on the host against n_push_max
+            const int f = sim_recorded_frame(st, a.record_every);
 #pragma unroll
             for (int k = 0; k < kBoxPer; ++k)
-                if (live[k]) {
-                    float *o = frames + ((size_t)f * a.n_max + t + kBoxThreads * k) * 3;
-                    o[0] = X + (co * qx[k] - si * qz[k]); o[1] = r; o[2] = Z + (si * qx[k] + co * qz[k]);
-                }
+                if (live[k])
+                    sim_store3(frames + ((size_t)f * a.n_max + t + kBoxThreads * k) * 3, X + (co * qx[k] - si * qz[k]), r, Z + (si * qx[k] + co * qz[k]));
             if (t == 0) {
-                tool[f * 3] = cx; tool[f * 3 + 1] = r; tool[f * 3 + 2] = cz;
+                sim_store3(tool + f * 3, cx, r, cz);
                 poses[f * 4] = X; poses[f * 4 + 1] = Z; poses[f * 4 + 2] = co; poses[f * 4 + 3] = si;
             }
         }
     }
-    const int f = (n_push - 1) / a.record_every + 1;
+    const int f = sim_final_frame(n_push, a.record_every);
 #pragma unroll
     for (int k = 0; k < kBoxPer; ++k)
-        if (live[k]) {
-            float *o = frames + ((size_t)f * a.n_max + t + kBoxThreads * k) * 3;
-            o[0] = X + (co * qx[k] - si * qz[k]); o[1] = r; o[2] = Z + (si * qx[k] + co * qz[k]);
-        }
+        if (live[k])
+            sim_store3(frames + ((size_t)f * a.n_max + t + kBoxThreads * k) * 3, X + (co * qx[k] - si * qz[k]), r, Z + (si * qx[k] + co * qz[k]));
     if (t == 0) {
-        tool[f * 3] = xe; tool[f * 3 + 1] = r + a.lift; tool[f * 3 + 2] = ze;
+        sim_store3(tool + f * 3, xe, r + a.lift, ze);
         poses[f * 4] = X; poses[f * 4 + 1] = Z; poses[f * 4 + 2] = co; poses[f * 4 + 3] = si;
         a.pose[4 * e] = X; a.pose[4 * e + 1] = Z; a.pose[4 * e + 2] = co; a.pose[4 * e + 3] = si;
         a.vel[3 * e] = VX; a.vel[3 * e + 1] = VZ; a.vel[3 * e + 2] = Om;
         a.n_frames[e] = f + 1;
     }
 }
-
-int box_frames(int n_push, int record_every) { return (n_push - 1) / record_every + 2; }
 
 }  // namespace
 
@@ -198,16 +189,9 @@ int ag_sim_box_push(const int32_t *n, const float *q, const float *m, const floa
 {
     if (!n || !q || !m || !body || !inv || !n_push || !push || !pose || !vel || !obj || !eef || !pose_frames || !n_frames)
         return ag_fail(AG_ERR_ARG, "ag_sim_box_push: null argument");
-    if (E < 1) return ag_fail(AG_ERR_ARG, "ag_sim_box_push: E = %d episodes", E);
-    if (n_max < 4 || n_max > AG_SIM_BOX_MAX_PARTICLES)
-        return ag_fail(AG_ERR_ARG, "ag_sim_box_push: n_max = %d outside 4 .. %d (AG_SIM_BOX_MAX_PARTICLES)", n_max, AG_SIM_BOX_MAX_PARTICLES);
-    if (n_push_max < 1 || substeps < 1 || iters < 1 || record_every < 1 || settle < 0 || n_push_max > INT32_MAX / substeps - settle - 1)
-        return ag_fail(AG_ERR_ARG, "ag_sim_box_push: n_push_max = %d substeps = %d iters = %d record_every = %d settle = %d", n_push_max,
-                       substeps, iters, record_every, settle);
-    if (F_max < box_frames(n_push_max, record_every))
-        return ag_fail(AG_ERR_ARG, "ag_sim_box_push: F_max = %d frames, a push of %d steps recorded every %d writes %d", F_max, n_push_max,
-                       record_every, box_frames(n_push_max, record_every));
-    if (!(h > 0.f)) return ag_fail(AG_ERR_ARG, "ag_sim_box_push: substep h = %g", (double)h);
+    if (int err = sim_check_schedule("ag_sim_box_push", E, n_max, 4, AG_SIM_BOX_MAX_PARTICLES, "AG_SIM_BOX_MAX_PARTICLES", F_max, n_push_max, 1,
+                                     substeps, true, iters, record_every, settle, h, "push"))
+        return err;
     if (!(eps > 0.f) || !((mu * g) / eps <= kBoxKMax))      // with |rho| <= 8 this keeps 1024 scaled terms inside 2^51
         return ag_fail(AG_ERR_ARG, "ag_sim_box_push: (mu g) / eps = %g outside (0, %g]", (double)((mu * g) / eps), (double)kBoxKMax);
     BoxPushArgs a{n, n_push, q, m, body, inv, push, pose, vel, obj, eef, pose_frames, n_frames, n_max, F_max, n_push_max, substeps, iters,

@@ -1,12 +1,12 @@
 // ag_sim_cloth.hip — a batched mass-spring cloth simulator: one grasp-and-drag of E cloth episodes in one launch.  Like ag_sim.hip and
 // ag_sim_pile.hip it stands in for the data side of the reference (src/sim/sim_env/flex_env.py:258-402 steps a closed CUDA solver); the model is
-// this project's own (not FleX, no self-collision), stated operation for operation in adaptigraph_amd/sim.py (cloth_push_host, the float32 numpy
+// this project's own (not FleX, no self-collision), stated operation for operation in adaptigraph_amd/sim/cloth.py (cloth_push_host, the float32 numpy
 // statement) and repeated here so that both give the same bits.
 //
 // One 1024-thread workgroup owns an episode for the whole call, four particles per thread (particle i = t + 1024 k, n = nx nz <= 4096).  A
 // particle's position at the start of the substep and its velocity stay in registers; LDS holds ONE copy of the predicted positions of all
 // particles (three planes of 4096 floats, 48 KB) and their inverse masses (4096 bytes): the constraint sweep is a coloured Gauss-Seidel pass in
-// place.  A sweep is twelve phases (sim.py has the order); within a phase no particle belongs to two pairs, so the threads of a phase touch
+// place.  A sweep is twelve phases (sim/cloth.py has the order); within a phase no particle belongs to two pairs, so the threads of a phase touch
 // disjoint words and its result does not depend on which thread takes which pair: that is the whole basis of the equality with the host.  A
 // phase maps its pair keys q = 0 .. rows cols - 1 over the threads (q = t + 1024 m), splits q into (row a, column b) with a multiply-high by
 // a precomputed reciprocal (exact for q < 4096 and divisors <= 64), and ends in a workgroup barrier: 1 + 12 iters barriers per substep.
@@ -15,7 +15,7 @@
 // 64-bit keys (bits of d2) << 32 | index (block_min_u64: an integer minimum, exact in any order; equal d2 goes to the lower index).
 // No atomics, no float reductions.  Every product is rounded on its own (-ffp-contract=off), division and square root are the correctly
 // rounded ones.
-#include "ag_host.h"
+#include "ag_sim_dev.h"
 #include "ag_block_dev.h"
 
 namespace {
@@ -98,10 +98,8 @@ __global__ __launch_bounds__(kClothThreads) void cloth_push_kernel(const ClothPu
     const int e = blockIdx.x, t = threadIdx.x;
     const int nx = a.nx[e], nz = a.nz[e], n1 = a.steps[2 * e], n2 = a.steps[2 * e + 1];
     if (nx < 2 || nx > kClothSide || nz < 2 || nz > kClothSide || nx * nz > a.n_max || n1 < 1 || n2 < 1 || n1 > a.n_push_max ||
-        n2 > a.n_push_max - n1) {      // (uniform) no frame, nothing touched
-        if (t == 0) a.n_frames[e] = 0;
-        return;
-    }
+        n2 > a.n_push_max - n1)
+        return sim_no_frame(a.n_frames, e, t);
     const int n = nx * nz, n_push = n1 + n2;
     const float l0 = a.rest[2 * e], lsh = a.rest[2 * e + 1], l2 = l0 * 2.f;
     const float ks = a.gains[4 * e], kh = a.gains[4 * e + 1], kb = a.gains[4 * e + 2], mu = a.gains[4 * e + 3];
@@ -174,10 +172,10 @@ __global__ __launch_bounds__(kClothThreads) void cloth_push_kernel(const ClothPu
         for (int s = 0; s < S; ++s) {
             // b'. the gripper's point of this substep
             if (st < n1) {
-                const float tt = (float)(st * S + s + 1) * inv1;
+                const float tt = sim_substep_t(st, S, s, inv1);
                 cx = xs + (xe - xs) * tt; cy = lift * tt; cz = zs + (ze - zs) * tt;
             } else if (held) {
-                const float tt = (float)((st - n1) * S + s + 1) * inv2;
+                const float tt = sim_substep_t(st - n1, S, s, inv2);
                 cx = xe; cy = fmaxf(lift - lift * tt, 0.f); cz = ze;
             }
             // a. predict, b. pins.  The planes were last read by their owners (below) and by the last phase, both before that phase's barrier
@@ -210,8 +208,7 @@ __global__ __launch_bounds__(kClothThreads) void cloth_push_kernel(const ClothPu
                 float wx = (px - x[k]) / h, wz = (pz - z[k]) / h;
                 const float wy = (py - y[k]) / h;
                 if (on && !pin[k]) {
-                    const float sp = sqrtf(wx * wx + wz * wz);
-                    const float f = sp > mgh ? 1.f - mgh / sp : 0.f;
+                    const float f = sim_coulomb(wx, wz, mgh);
                     wx = wx * f; wz = wz * f;
                 }
                 vx[k] = wx; vy[k] = wy; vz[k] = wz;
@@ -219,29 +216,25 @@ __global__ __launch_bounds__(kClothThreads) void cloth_push_kernel(const ClothPu
             }
         }
         if (held && st % a.record_every == 0) {
-            const int f = st / a.record_every;                               // < F_max: checked on the host against n_push_max
+            const int f = sim_recorded_frame(st, a.record_every);
 #pragma unroll
             for (int k = 0; k < kClothPer; ++k)
-                if (live[k]) {
-                    float *o = frames + ((size_t)f * a.n_max + t + kClothThreads * k) * 3;
-                    o[0] = x[k]; o[1] = y[k]; o[2] = z[k];
-                }
+                if (live[k]) sim_store3(frames + ((size_t)f * a.n_max + t + kClothThreads * k) * 3, x[k], y[k], z[k]);
             if (t < 2) {
                 float *o = tool + (f * 2 + t) * 3;
                 o[0] = t == 0 ? cx + fx : cx - fx; o[1] = a.tool_y + cy; o[2] = t == 0 ? cz + fz : cz - fz;
             }
         }
     }
-    const int f = (n_push - 1) / a.record_every + 1;
+    const int f = sim_final_frame(n_push, a.record_every);
 #pragma unroll
     for (int k = 0; k < kClothPer; ++k)
         if (live[k]) {
             const int i = t + kClothThreads * k;
-            float *o = frames + ((size_t)f * a.n_max + i) * 3;
-            o[0] = x[k]; o[1] = y[k]; o[2] = z[k];
+            sim_store3(frames + ((size_t)f * a.n_max + i) * 3, x[k], y[k], z[k]);
             const size_t row = ((size_t)e * a.n_max + i) * 3;
-            a.x[row] = x[k]; a.x[row + 1] = y[k]; a.x[row + 2] = z[k];
-            a.v[row] = vx[k]; a.v[row + 1] = vy[k]; a.v[row + 2] = vz[k];
+            sim_store3(a.x + row, x[k], y[k], z[k]);
+            sim_store3(a.v + row, vx[k], vy[k], vz[k]);
         }
     if (t < 2) {
         float *o = tool + (f * 2 + t) * 3;
@@ -249,8 +242,6 @@ __global__ __launch_bounds__(kClothThreads) void cloth_push_kernel(const ClothPu
     }
     if (t == 0) a.n_frames[e] = f + 1;
 }
-
-int cloth_frames(int n_push, int record_every) { return (n_push - 1) / record_every + 2; }
 
 }  // namespace
 
@@ -263,16 +254,9 @@ int ag_sim_cloth_push(const int32_t *nx, const int32_t *nz, const float *rest, c
 {
     if (!nx || !nz || !rest || !gains || !steps || !inv || !action || !lat || !x || !v || !obj || !eef || !n_frames || !picked)
         return ag_fail(AG_ERR_ARG, "ag_sim_cloth_push: null argument");
-    if (E < 1) return ag_fail(AG_ERR_ARG, "ag_sim_cloth_push: E = %d episodes", E);
-    if (n_max < 4 || n_max > AG_SIM_CLOTH_MAX_PARTICLES)
-        return ag_fail(AG_ERR_ARG, "ag_sim_cloth_push: n_max = %d outside 4 .. %d (AG_SIM_CLOTH_MAX_PARTICLES)", n_max, AG_SIM_CLOTH_MAX_PARTICLES);
-    if (n_push_max < 2 || substeps < 1 || iters < 1 || record_every < 1 || settle < 0 || n_push_max > INT32_MAX / substeps - settle - 1)
-        return ag_fail(AG_ERR_ARG, "ag_sim_cloth_push: n_push_max = %d substeps = %d iters = %d record_every = %d settle = %d", n_push_max,
-                       substeps, iters, record_every, settle);
-    if (F_max < cloth_frames(n_push_max, record_every))
-        return ag_fail(AG_ERR_ARG, "ag_sim_cloth_push: F_max = %d frames, a drag of %d steps recorded every %d writes %d", F_max, n_push_max,
-                       record_every, cloth_frames(n_push_max, record_every));
-    if (!(h > 0.f)) return ag_fail(AG_ERR_ARG, "ag_sim_cloth_push: substep h = %g", (double)h);
+    if (int err = sim_check_schedule("ag_sim_cloth_push", E, n_max, 4, AG_SIM_CLOTH_MAX_PARTICLES, "AG_SIM_CLOTH_MAX_PARTICLES", F_max, n_push_max, 2,
+                                     substeps, true, iters, record_every, settle, h, "drag"))
+        return err;
     ClothPushArgs a{nx, nz, steps, rest, gains, inv, action, lat, x, v, obj, eef, n_frames, picked, n_max, F_max, n_push_max, substeps, iters,
                     record_every, settle, h, g, r, damp, lift, grasp2, finger, tool_y};
     hipLaunchKernelGGL(cloth_push_kernel, dim3(E), dim3(kClothThreads), 0, static_cast<hipStream_t>(stream), a);

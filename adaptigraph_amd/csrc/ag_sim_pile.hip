@@ -1,6 +1,6 @@
 // ag_sim_pile.hip — a batched disc-pile-on-table simulator: one board push of E granular episodes in one launch.  Like ag_sim.hip it stands in
 // for the data side of the reference (src/sim/sim_env/flex_env.py:258-402 steps a closed CUDA solver); the model is this project's own, stated
-// operation for operation in adaptigraph_amd/sim.py (pile_push_host, the float32 numpy statement) and repeated here so that both give the same bits.
+// operation for operation in adaptigraph_amd/sim/pile.py (pile_push_host, the float32 numpy statement) and repeated here so that both give the same bits.
 //
 // One 256-thread workgroup owns an episode for the whole push, four grains per thread (grain i = t + 256 k, n <= 1024).  A grain's position at
 // the start of the substep and its velocity stay in registers; LDS holds the predicted positions of all grains twice
@@ -19,7 +19,7 @@
 // are integers.  No global atomics, no float atomics.  Whether an episode pushes or records, its n and its iteration count are uniform over its
 // workgroup, so every barrier is reached by all 256 threads.  Every product is rounded on its own (-ffp-contract=off), division and square root
 // are the correctly rounded ones.
-#include "ag_host.h"
+#include "ag_sim_dev.h"
 #include "ag_block_dev.h"
 
 namespace {
@@ -56,10 +56,7 @@ __global__ __launch_bounds__(kPileThreads) void pile_push_kernel(const PilePushA
     const int e = blockIdx.x, t = threadIdx.x;
     const int n = a.n[e], n_push = a.n_push[e];
     const float rho = a.rho[e];
-    if (n < 1 || n > a.n_max || n_push < 1 || n_push > a.n_push_max || !(rho > 0.f) || rho > a.rho_max) {      // (uniform) no frame, nothing touched
-        if (t == 0) a.n_frames[e] = 0;
-        return;
-    }
+    if (n < 1 || n > a.n_max || n_push < 1 || n_push > a.n_push_max || !(rho > 0.f) || rho > a.rho_max) return sim_no_frame(a.n_frames, e, t);
     const float inv = a.inv[e];
     const float sx = a.push[4 * e], sz = a.push[4 * e + 1], ex = a.push[4 * e + 2], ez = a.push[4 * e + 3];
     const float ux = a.lat[2 * e], uz = a.lat[2 * e + 1];
@@ -142,8 +139,7 @@ __global__ __launch_bounds__(kPileThreads) void pile_push_kernel(const PilePushA
                 if (live[k]) { px[k] = s_px[a.iters & 1][t + kPileThreads * k]; pz[k] = s_pz[a.iters & 1][t + kPileThreads * k]; }
             // c. board
             if (pushing) {
-                const float tt = (float)(st * S + s + 1) * inv;
-                cx = sx + (ex - sx) * tt; cz = sz + (ez - sz) * tt;
+                sim_tool_centre(cx, cz, sx, sz, ex, ez, sim_substep_t(st, S, s, inv));
 #pragma unroll
                 for (int k = 0; k < kPilePer; ++k) {
                     const float ax = px[k] - cx, az = pz[k] - cz;
@@ -163,30 +159,25 @@ __global__ __launch_bounds__(kPileThreads) void pile_push_kernel(const PilePushA
 #pragma unroll
             for (int k = 0; k < kPilePer; ++k) {
                 const float wx_ = (px[k] - x[k]) / h, wz_ = (pz[k] - z[k]) / h;
-                const float sp = sqrtf(wx_ * wx_ + wz_ * wz_);
-                const float f = sp > mgh ? 1.f - mgh / sp : 0.f;
+                const float f = sim_coulomb(wx_, wz_, mgh);
                 vx[k] = wx_ * f; vz[k] = wz_ * f;
                 x[k] = px[k]; z[k] = pz[k];
             }
         }
         if (pushing && st % a.record_every == 0) {
-            const int f = st / a.record_every;                               // < F_max: checked on the host against n_push_max
+            const int f = sim_recorded_frame(st, a.record_every);
 #pragma unroll
             for (int k = 0; k < kPilePer; ++k)
-                if (live[k]) {
-                    float *o = frames + ((size_t)f * a.n_max + t + kPileThreads * k) * 3;
-                    o[0] = x[k]; o[1] = y[k]; o[2] = z[k];
-                }
+                if (live[k]) sim_store3(frames + ((size_t)f * a.n_max + t + kPileThreads * k) * 3, x[k], y[k], z[k]);
             if (t < 5) { tool[(f * 5 + t) * 3] = cx + off * ux; tool[(f * 5 + t) * 3 + 1] = a.tool_y; tool[(f * 5 + t) * 3 + 2] = cz + off * uz; }
         }
     }
-    const int f = (n_push - 1) / a.record_every + 1;
+    const int f = sim_final_frame(n_push, a.record_every);
 #pragma unroll
     for (int k = 0; k < kPilePer; ++k)
         if (live[k]) {
             const int i = t + kPileThreads * k;
-            float *o = frames + ((size_t)f * a.n_max + i) * 3;
-            o[0] = x[k]; o[1] = y[k]; o[2] = z[k];
+            sim_store3(frames + ((size_t)f * a.n_max + i) * 3, x[k], y[k], z[k]);
             const size_t row = ((size_t)e * a.n_max + i) * 3;
             a.x[row] = x[k]; a.x[row + 2] = z[k];
             a.v[row] = vx[k]; a.v[row + 2] = vz[k];
@@ -194,8 +185,6 @@ __global__ __launch_bounds__(kPileThreads) void pile_push_kernel(const PilePushA
     if (t < 5) { tool[(f * 5 + t) * 3] = ex + off * ux; tool[(f * 5 + t) * 3 + 1] = a.tool_y + a.lift; tool[(f * 5 + t) * 3 + 2] = ez + off * uz; }
     if (t == 0) a.n_frames[e] = f + 1;
 }
-
-int pile_frames(int n_push, int record_every) { return (n_push - 1) / record_every + 2; }
 
 }  // namespace
 
@@ -208,16 +197,9 @@ int ag_sim_pile_push(const int32_t *n, const float *rho, const float *inv, const
 {
     if (!n || !rho || !inv || !n_push || !push || !lat || !x || !v || !obj || !eef || !n_frames)
         return ag_fail(AG_ERR_ARG, "ag_sim_pile_push: null argument");
-    if (E < 1) return ag_fail(AG_ERR_ARG, "ag_sim_pile_push: E = %d episodes", E);
-    if (n_max < 1 || n_max > AG_SIM_PILE_MAX_PARTICLES)
-        return ag_fail(AG_ERR_ARG, "ag_sim_pile_push: n_max = %d outside 1 .. %d (AG_SIM_PILE_MAX_PARTICLES)", n_max, AG_SIM_PILE_MAX_PARTICLES);
-    if (n_push_max < 1 || substeps < 1 || iters < 1 || record_every < 1 || settle < 0 || n_push_max > INT32_MAX / substeps - settle - 1)
-        return ag_fail(AG_ERR_ARG, "ag_sim_pile_push: n_push_max = %d substeps = %d iters = %d record_every = %d settle = %d", n_push_max,
-                       substeps, iters, record_every, settle);
-    if (F_max < pile_frames(n_push_max, record_every))
-        return ag_fail(AG_ERR_ARG, "ag_sim_pile_push: F_max = %d frames, a push of %d steps recorded every %d writes %d", F_max, n_push_max,
-                       record_every, pile_frames(n_push_max, record_every));
-    if (!(h > 0.f)) return ag_fail(AG_ERR_ARG, "ag_sim_pile_push: substep h = %g", (double)h);
+    if (int err = sim_check_schedule("ag_sim_pile_push", E, n_max, 1, AG_SIM_PILE_MAX_PARTICLES, "AG_SIM_PILE_MAX_PARTICLES", F_max, n_push_max, 1,
+                                     substeps, true, iters, record_every, settle, h, "push"))
+        return err;
     if (!(rho_max > 0.f) || rho_max > 0.25f)      // 1023 contact terms of at most rho 2^22 each must fit int32
         return ag_fail(AG_ERR_ARG, "ag_sim_pile_push: rho_max = %g outside (0, 0.25]", (double)rho_max);
     PilePushArgs a{n, n_push, rho, inv, push, lat, x, v, obj, eef, n_frames, n_max, F_max, n_push_max, substeps, iters, record_every, settle,

@@ -1,4 +1,4 @@
-"""Rope, granular, cloth and box datasets from the particle simulators (sim.py), written in the layout `load.py` reads — the work of the reference's
+"""Rope, granular, cloth and box datasets from the particle simulators (sim/), written in the layout `load.py` reads — the work of the reference's
 src/sim/data_gen/data_gen.py followed by src/dynamics/preprocess/preprocess.py:135-230, without the .h5 files in between.
 
     python -m adaptigraph_amd.datagen --out DIR --episodes 64 --pushes 5                          # rope
@@ -98,6 +98,37 @@ def _write_dataset(root, ds, properties, phys, pairs, eef_pos, obj_pos):
     return dict(ds, data_dir=data_dir, prep_data_dir=prep_dir)
 
 
+def _take_xv(scene, out):
+    """The results of a rope, pile or cloth push: obj, eef, n_frames first, the new x, v last, which go back into the scene."""
+    scene.x, scene.v = out[-2:]
+    return out[0], out[1], out[2], None
+
+
+def _simulate(ds, scene, rngs, n_pushes, sample, host_push, device_push, params, device, take=_take_xv):
+    """The loop of every dataset.  Push k: sample(e) draws episode e's push from the scene as it lies; ALL episodes are one `device_push` call
+    on `device`, read back once (device=None: `host_push`); take(scene, results) writes the new state into the scene and returns obj
+    (E, F, n_max, 3), eef (E, F, 3) or (E, F, tools, 3), n_frames (E) and per-frame extras (E, F, ...) or None.
+    -> pairs {(e, k): rows}, eef_pos, obj_pos, extras: per episode the list of its pushes' (frames, ...) arrays."""
+    E = len(rngs)
+    eef_pos, obj_pos, extras, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [[] for _ in rngs], [0] * E, {}
+    for k in range(n_pushes):
+        push = np.stack([sample(e) for e in range(E)])
+        if device is None:
+            out = host_push(scene, push, params)
+        else:
+            out = tuple(t.cpu().numpy() for t in device_push(scene, push, params, device=device))
+        obj, eef, nf, extra = take(scene, out)
+        for e in range(E):
+            tool = eef[e, :nf[e]] if eef.ndim == 4 else eef[e, :nf[e], None, :]
+            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
+            n_frames[e] += cnt
+            eef_pos[e].append(tool)
+            obj_pos[e].append(obj[e, :nf[e], :scene.n[e]])
+            if extra is not None:
+                extras[e].append(extra[e, :nf[e]])
+    return pairs, eef_pos, obj_pos, extras
+
+
 def generate_granular_dataset(root, n_episodes, n_pushes, seed=0, device=None, dataset_config=None, params=sim.PILE_DEFAULT,
                               area_range=(1.0, 9.0)):
     """Simulate n_episodes piles through n_pushes board pushes each and write the dataset under `root`.  Episode e draws its pile
@@ -109,20 +140,8 @@ def generate_granular_dataset(root, n_episodes, n_pushes, seed=0, device=None, d
     rngs = [np.random.default_rng(seed + e) for e in range(n_episodes)]
     piles, scales = zip(*(sim.initial_pile(rng, area_range) for rng in rngs))
     scene = sim.PileScene.from_piles(piles, [s / 2 for s in scales])
-    eef_pos, obj_pos, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes, {}
-    for k in range(n_pushes):
-        push = np.stack([sim.sample_board_push(scene.x[e, :scene.n[e]], scene.rho[e], rngs[e], params) for e in range(n_episodes)])
-        if device is None:
-            obj, eef, nf, x, v = sim.pile_push_host(scene, push, params)
-        else:
-            obj, eef, nf, x, v = (t.cpu().numpy() for t in sim.pile_push(scene, push, params, device=device))
-        scene.x, scene.v = x, v
-        for e in range(n_episodes):
-            tool = eef[e, :nf[e]]
-            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
-            n_frames[e] += cnt
-            eef_pos[e].append(tool)
-            obj_pos[e].append(obj[e, :nf[e], :scene.n[e]])
+    sample = lambda e: sim.sample_board_push(scene.x[e, :scene.n[e]], scene.rho[e], rngs[e], params)
+    pairs, eef_pos, obj_pos, _ = _simulate(ds, scene, rngs, n_pushes, sample, sim.pile_push_host, sim.pile_push, params, device)
     properties = [{"particle_radius": float(scene.rho[e]), "granular_scale": float(scales[e]), "num_granular": int(scene.n[e])}
                   for e in range(n_episodes)]
     return _write_dataset(root, ds, properties, scales, pairs, eef_pos, obj_pos)
@@ -145,20 +164,8 @@ def generate_cloth_dataset(root, n_episodes, n_pushes, seed=0, device=None, data
     scene = sim.ClothScene.from_cloths([c for c, _ in cloths], sf=sf, l0=[l0 for _, l0 in cloths])
     n = scene.n
     borders = [sim.cloth_border(int(scene.nx[e]), int(scene.nz[e])) for e in range(n_episodes)]
-    eef_pos, obj_pos, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes, {}
-    for k in range(n_pushes):
-        action = np.stack([sim.sample_grasp(scene.x[e, :n[e]], borders[e], rngs[e], params, nx=scene.nx[e]) for e in range(n_episodes)])
-        if device is None:
-            obj, eef, nf, _, x, v = sim.cloth_push_host(scene, action, params)
-        else:
-            obj, eef, nf, _, x, v = (t.cpu().numpy() for t in sim.cloth_push(scene, action, params, device=device))
-        scene.x, scene.v = x, v
-        for e in range(n_episodes):
-            tool = eef[e, :nf[e]]
-            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
-            n_frames[e] += cnt
-            eef_pos[e].append(tool)
-            obj_pos[e].append(obj[e, :nf[e], :n[e]])
+    sample = lambda e: sim.sample_grasp(scene.x[e, :n[e]], borders[e], rngs[e], params, nx=scene.nx[e])
+    pairs, eef_pos, obj_pos, _ = _simulate(ds, scene, rngs, n_pushes, sample, sim.cloth_push_host, sim.cloth_push, params, device)
     properties = [{"particle_radius": float(params.r), "sf": float(sf[e]), "stretch_stiffness": float(scene.ks[e]),
                    "bend_stiffness": float(scene.kb[e]), "shear_stiffness": float(scene.kh[e]), "dynamic_friction": float(scene.mu[e])}
                   for e in range(n_episodes)]
@@ -175,31 +182,22 @@ def generate_box_dataset(root, n_episodes, n_pushes, seed=0, device=None, datase
     rngs = [np.random.default_rng(seed + e) for e in range(n_episodes)]
     sizes, coms, angles = zip(*(sim.initial_box(rng) for rng in rngs))
     scene = sim.BoxScene.from_boxes(sizes, coms, angles, r=params.r)
-    eef_pos, obj_pos, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes, {}
-    states = [[] for _ in rngs]
-    for k in range(n_pushes):
-        push = np.stack([sim.sample_box_push(scene.row(e), rngs[e], push_length) for e in range(n_episodes)])
-        if device is None:
-            obj, eef, poses, nf, pose, vel = sim.box_push_host(scene, push, params)
-        else:
-            obj, eef, poses, nf, pose, vel = (t.cpu().numpy() for t in sim.box_push(scene, push, params, device=device))
-        scene.pose, scene.vel = pose, vel
-        scene.x = sim.box_particles(pose, scene.q, scene.n, params.r)
-        for e in range(n_episodes):
-            tool = eef[e, :nf[e], None, :]
-            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
-            n_frames[e] += cnt
-            eef_pos[e].append(tool)
-            obj_pos[e].append(obj[e, :nf[e], :scene.n[e]])
-            p = poses[e, :nf[e]].astype(np.float64)
-            states[e].append(np.stack([p[:, 0], p[:, 1], np.arctan2(p[:, 3], p[:, 2])], 1))
+
+    def take(scene, out):
+        obj, eef, poses, nf, scene.pose, scene.vel = out
+        scene.x = sim.box_particles(scene.pose, scene.q, scene.n, params.r)
+        return obj, eef, nf, poses
+
+    sample = lambda e: sim.sample_box_push(scene.row(e), rngs[e], push_length)
+    pairs, eef_pos, obj_pos, poses = _simulate(ds, scene, rngs, n_pushes, sample, sim.box_push_host, sim.box_push, params, device, take)
     properties = [{"particle_radius": float(params.r), "box_width": float(scene.size[e, 0]), "box_height": float(scene.size[e, 1]),
                    "com_x": float(scene.com[e, 0]) + 0.5, "com_y": float(scene.com[e, 1]) + 0.5} for e in range(n_episodes)]
     phys = np.array([[p["com_x"], p["com_y"]] for p in properties])
     out = _write_dataset(root, ds, properties, phys, pairs, eef_pos, obj_pos)
     for e in range(n_episodes):
         epi = os.path.join(out["data_dir"], ds["data_name"], f"{e:06}")
-        np.save(os.path.join(epi, "box_states.npy"), np.concatenate(states[e]))
+        p = np.concatenate(poses[e]).astype(np.float64)
+        np.save(os.path.join(epi, "box_states.npy"), np.stack([p[:, 0], p[:, 1], np.arctan2(p[:, 3], p[:, 2])], 1))
         np.save(os.path.join(epi, "eef_states.npy"), np.concatenate(eef_pos[e])[:, 0, [0, 2]].astype(np.float64))
         size = scene.size[e].astype(np.float64)
         np.save(os.path.join(epi, "box_com.npy"), np.stack([size, scene.com[e].astype(np.float64) * size]))
@@ -216,20 +214,8 @@ def generate_rope_dataset(root, n_episodes, n_pushes, seed=0, device=None, datas
     ropes = [sim.initial_rope(rng, n_particles, params.r) for rng in rngs]
     stiffness = np.array([rng.uniform(0.0, 1.0) for rng in rngs])
     scene = sim.RopeScene.from_ropes(ropes, stiffness=stiffness)
-    eef_pos, obj_pos, n_frames, pairs = [[] for _ in rngs], [[] for _ in rngs], [0] * n_episodes, {}
-    for k in range(n_pushes):
-        push = np.stack([sim.sample_push(scene.x[e, :scene.n[e]], rngs[e], params) for e in range(n_episodes)])
-        if device is None:
-            obj, eef, nf, x, v = sim.rope_push_host(scene, push, params)
-        else:
-            obj, eef, nf, x, v = (t.cpu().numpy() for t in sim.rope_push(scene, push, params, device=device))
-        scene.x, scene.v = x, v
-        for e in range(n_episodes):
-            tool = eef[e, :nf[e], None, :]
-            pairs[e, k], cnt = preprocess.extract_push(tool, ds["dist_thresh"], ds["n_his"], ds["n_future"], n_frames[e])
-            n_frames[e] += cnt
-            eef_pos[e].append(tool)
-            obj_pos[e].append(obj[e, :nf[e], :scene.n[e]])
+    sample = lambda e: sim.sample_push(scene.x[e, :scene.n[e]], rngs[e], params)
+    pairs, eef_pos, obj_pos, _ = _simulate(ds, scene, rngs, n_pushes, sample, sim.rope_push_host, sim.rope_push, params, device)
     properties = [{"particle_radius": float(params.r), "stiffness": float(stiffness[e])} for e in range(n_episodes)]
     return _write_dataset(root, ds, properties, stiffness, pairs, eef_pos, obj_pos)
 
@@ -245,20 +231,12 @@ def main(argv=None):
     ap.add_argument("--device", default="cuda:0", help="a GPU, or 'host' for the numpy restatement (slow)")
     args = ap.parse_args(argv)
     device = None if args.device == "host" else args.device
-    if args.material == "granular":
-        ds = generate_granular_dataset(args.out, args.episodes, args.pushes, args.seed, device)
-        print(f"{args.episodes} episodes x {args.pushes} pushes of granular piles under {ds['data_dir']} and {ds['prep_data_dir']}")
-        return
-    if args.material == "cloth":
-        ds = generate_cloth_dataset(args.out, args.episodes, args.pushes, args.seed, device)
-        print(f"{args.episodes} episodes x {args.pushes} grasp-and-drags of cloths under {ds['data_dir']} and {ds['prep_data_dir']}")
-        return
-    if args.material == "box":
-        ds = generate_box_dataset(args.out, args.episodes, args.pushes, args.seed, device)
-        print(f"{args.episodes} episodes x {args.pushes} pushes of boxes under {ds['data_dir']} and {ds['prep_data_dir']}")
-        return
-    ds = generate_rope_dataset(args.out, args.episodes, args.pushes, args.seed, device, n_particles=args.particles)
-    print(f"{args.episodes} episodes x {args.pushes} pushes of {args.particles} particles under {ds['data_dir']} and {ds['prep_data_dir']}")
+    generate, what, kwargs = {"rope": (generate_rope_dataset, f"pushes of {args.particles} particles", {"n_particles": args.particles}),
+                              "granular": (generate_granular_dataset, "pushes of granular piles", {}),
+                              "cloth": (generate_cloth_dataset, "grasp-and-drags of cloths", {}),
+                              "box": (generate_box_dataset, "pushes of boxes", {})}[args.material]
+    ds = generate(args.out, args.episodes, args.pushes, args.seed, device, **kwargs)
+    print(f"{args.episodes} episodes x {args.pushes} {what} under {ds['data_dir']} and {ds['prep_data_dir']}")
 
 
 if __name__ == "__main__":

@@ -1,6 +1,6 @@
 """Simulated depth cameras: depth and id images of a particle scene from calibrated pinhole cameras, every particle a sphere, the table a plane
 (DESIGN.md §8.14).  It is what the reference takes from its simulator's renderer (`pyflex.render(render_depth=True)`, flex_env.py:151-189,
-:404-409), for the project's own simulators (sim.py): a sphere splat of their particles, NOT FleX's renderer, with no tool, no colour and no
+:404-409), for the project's own simulators (sim/): a sphere splat of their particles, NOT FleX's renderer, with no tool, no colour and no
 sensor noise.
 
 Two paths, one result.  `render_depth_host` is the statement of the arithmetic, in numpy; `render_depth(..., device=)` is one launch of

@@ -1,4 +1,4 @@
-"""`SimEnv`: a stand-in for the reference's `RealEnv` (src/planning/real_world/real_env.py:152-276) over the project's own simulators (sim.py),
+"""`SimEnv`: a stand-in for the reference's `RealEnv` (src/planning/real_world/real_env.py:152-276) over the project's own simulators (sim/),
 seen through simulated depth cameras (render.py).  It has RealEnv's observation and action surface -- `get_obs`, `get_intrinsics`,
 `get_extrinsics`, `get_bbox`, `step`, `step_gripper` -- so the loop of plan.py:229-315 (closed_loop.run_closed_loop) runs against it, and
 `get_state_cur`, which is perception.state_from_depth on the rendered images.
@@ -23,7 +23,12 @@ import numpy as np
 
 from . import perception, render, sim
 
-MATERIALS = ("rope", "granular", "cloth", "box")
+# material: (default parameters, host push, device call)
+SIMULATORS = {"rope": (sim.DEFAULT, sim.rope_push_host, sim.DevicePush),
+              "granular": (sim.PILE_DEFAULT, sim.pile_push_host, sim.DevicePilePush),
+              "cloth": (sim.CLOTH_DEFAULT, sim.cloth_push_host, sim.DeviceClothPush),
+              "box": (sim.BOX_DEFAULT, sim.box_push_host, sim.DeviceBoxPush)}
+MATERIALS = tuple(SIMULATORS)
 DEFAULT_BBOX = ((-0.7, 0.7), (-0.7, 0.7), (-0.5, 0.05))      # board frame, metres: the work area and everything above the table (z is down)
 
 
@@ -58,8 +63,7 @@ class SimEnv:
             raise ValueError("SimEnv: one episode per environment (E = 1)")
         self.material, self.task_config = material, task_config
         self.ratio = float(task_config["sim_real_ratio"])
-        self.params = params if params is not None else {"rope": sim.DEFAULT, "granular": sim.PILE_DEFAULT, "cloth": sim.CLOTH_DEFAULT,
-                                                              "box": sim.BOX_DEFAULT}[material]
+        self.params = params if params is not None else SIMULATORS[material][0]
         self.H, self.W = int(image_size[0]), int(image_size[1])
         self.stride, self.near, self.far = int(stride), float(near), float(far)
         self.R_list, self.t_list, self.intr_list = cameras if cameras is not None else render.default_cameras(self.ratio, self.H, self.W)
@@ -129,37 +133,19 @@ class SimEnv:
 
     # ---- RealEnv's action surface
     def _push(self, segment):
+        """One push: the last two results of the material's push are its new state (x, v; the box's pose and velocity).  The box's x, what
+        the cameras see, is the last frame of the push: frame frames_of(n_push) - 1, a number the host knows without reading anything back."""
         push = np.asarray(segment, np.float64).astype(np.float32).reshape(1, 4)
+        _, host, device_call = SIMULATORS[self.material]
+        if self.device is None:
+            out = host(self.scene, push, self.params)
+        else:
+            out = device_call(self.scene, push, self.params, device=self.device).validate().launch()
         if self.material == "box":
-            return self._push_box(push)
-        if self.device is None:
-            host = {"rope": sim.rope_push_host, "granular": sim.pile_push_host, "cloth": sim.cloth_push_host}[self.material]
-            x, v = host(self.scene, push, self.params)[-2:]
+            last = int(sim.frames_of(sim.push_steps(push, self.params)[0], self.params)[0]) - 1
+            self.scene = dataclasses.replace(self.scene, x=out[0][:, last], pose=out[-2], vel=out[-1])
         else:
-            if self.material == "rope":
-                call = sim.DevicePush(self.scene, push, self.params, device=self.device)
-                sim._validate(self.scene, call.steps, call.dims[2], self.params)
-            elif self.material == "granular":
-                call = sim.DevicePilePush(self.scene, push, self.params, device=self.device)
-                sim._pile_validate(self.scene, call.steps, call.dims[2], self.params)
-            else:
-                call = sim.DeviceClothPush(self.scene, push, self.params, device=self.device)
-                sim._cloth_validate(self.scene, call.host_steps, call.dims[2], self.params)
-            x, v = call.launch()[-2:]
-        self.scene = dataclasses.replace(self.scene, x=x, v=v)
-        return push[0]
-
-    def _push_box(self, push):
-        """The box keeps its pose and velocity (on the device, on the device path); x, what the cameras see, is the last frame of the push:
-        frame frames_of(n_push) - 1, a number the host knows without reading anything back."""
-        if self.device is None:
-            obj, _, _, n_frames, pose, vel = sim.box_push_host(self.scene, push, self.params)
-        else:
-            call = sim.DeviceBoxPush(self.scene, push, self.params, device=self.device)
-            sim._box_validate(self.scene, call.steps, call.dims[2], self.params)
-            obj, _, _, _, pose, vel = call.launch()
-            n_frames = sim.frames_of(call.steps, self.params)
-        self.scene = dataclasses.replace(self.scene, x=obj[:, int(n_frames[0]) - 1], pose=pose, vel=vel)
+            self.scene = dataclasses.replace(self.scene, x=out[-2], v=out[-1])
         return push[0]
 
     def step(self, action, decoded=False):
