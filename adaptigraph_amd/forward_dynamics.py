@@ -92,14 +92,21 @@ def _ragged_plan(rep_cols, device):
     actives = torch.empty((n_look, S1), dtype=torch.int32, device=rep_cols.device)
     for li in range(n_look):
         _lib.call("ag_rollout_order", rep_cols.device, rep_cols[li], bsz, orders[li], actives[li])
-    host = _pinned(n_look * S1, torch.int32, device).view(n_look, S1)
-    host.copy_(actives, non_blocking=True)
-    return orders, host
+    return orders, _to_pinned(actives, device)
 
 
 def _ragged_steps(active):
     """Model steps of a column from its pinned counts, or None where a sample runs longer than AG_RAGGED_MAX_STEPS (the plain call's case)."""
     return None if int(active[-1]) != 0 else int(torch.count_nonzero(active[:-1]))
+
+
+def _push_plan(order, active, rep):
+    """What one push of a ragged call runs as -> (n_steps, order, active) for rollout(): the column's own steps, order and pinned counts, or — a
+    push longer than the ragged call takes — the plain call on the batch as it is (no order, no counts; one more host read for its step count)."""
+    n_steps = _ragged_steps(active)
+    if n_steps is None:
+        return int(rep.max()), None, None
+    return n_steps, order, active
 
 
 def rollout_scripted(model, state0, action0, tool_pos, tool_delta, attrs, p_instance, phys, mask, tool_mask, thr_sq, topk,
@@ -142,7 +149,10 @@ def rollout_scripted(model, state0, action0, tool_pos, tool_delta, attrs, p_inst
 
 
 def _place_tool(task, decoded, theta, y, device):
-    """Tool key-points and per-step delta from a decoded action (forward_dynamics.py:42-81 / :237-276)."""
+    """Tool key-points and per-step delta from a decoded action (forward_dynamics.py:42-81 / :237-276).
+    The reference-shaped form, for the two differentiable drivers; the no-grad drivers take _place_tool_lean, the same bits in fewer launches
+    (tests/test_host_logic.py, with this form as the reference).  The two must not be merged: this one's backward accumulates the five key-points'
+    gradients slice by slice, the lean form's would sum them in one broadcast reduction — another order, other gradient bits."""
     bsz = decoded.shape[0]
     pts = task["pusher_points"]
     ratio = task["sim_real_ratio"]
@@ -186,9 +196,7 @@ def _place_tool_lean(task, decoded, theta, y, device, zero=None):
         eef = torch.stack([decoded[:, 0], yy, decoded[:, 1]], dim=-1)[:, None]
     elif n_t == 5:
         key = ("pusher_off", tuple(float(pts[i][1]) * ratio for i in range(1, 5)), str(device))      # (a host list -> device tensor is a synchronising copy: once per pusher)
-        off = _OFFSETS.get(key)
-        if off is None:
-            off = _OFFSETS[key] = torch.tensor([0.0] + list(key[1]), device=device)      # (key-point 0: x + 0 * sin is x + 0)
+        off = _memo(_OFFSETS, key, lambda: torch.tensor([0.0] + list(key[1]), device=device))      # (key-point 0: x + 0 * sin is x + 0)
         sn, cs = torch.sin(theta), torch.cos(theta)
         ex = decoded[:, 0:1] + off[None] * sn[:, None]
         ez = decoded[:, 1:2] - off[None] * cs[:, None]
@@ -215,17 +223,35 @@ def _physics(ppm_optimizer, physics_param, bsz, device):
 _CONST = collections.OrderedDict()      # per (batch, particles, tools, instances, device): the call-invariant inputs of dynamics(), LRU of _CONST_MAX
 _CONST_MAX = 4                          # entries (an MPPI loop alternates between its chunk size and the bsz = 1 best-sample rollout: 2 live keys)
 _CONST_MAX_BYTES = 256 << 20            # and device bytes (20 000 samples x 200 particles: 66 MB per entry)
-_PINNED = {}
+_PINNED = {}                            # per (length, dtype, device): pinned staging buffers of _to_pinned
 _OFFSETS = {}                           # per (pusher geometry, device): key-point offsets of _place_tool_lean
+_LANES = {}                             # per device: the lane indices 0 .. 63 of block_sum
 
 
-def _pinned(n, dtype, device):
-    """One pinned host buffer per (length, dtype, device): streams of different devices never share a staging buffer."""
-    key = (n, dtype, str(device))
-    t = _PINNED.get(key)
-    if t is None:
-        t = _PINNED[key] = torch.empty(n, dtype=dtype, pin_memory=True)
-    return t
+def _memo(cache, key, make):
+    """cache[key], made by make() on first use: the small per-device tables above, whose first construction is an allocation or a synchronising copy."""
+    value = cache.get(key)
+    if value is None:
+        value = cache[key] = make()
+    return value
+
+
+def _to_pinned(t, device):
+    """t on its way to pinned host memory -> the host tensor of t's shape, valid once the stream has been synchronised (_host_read).  One buffer per
+    (length, dtype, device): streams of different devices never share a staging buffer."""
+    host = _memo(_PINNED, (t.numel(), t.dtype, str(device)), lambda: torch.empty(t.numel(), dtype=t.dtype, pin_memory=True)).view(t.shape)
+    host.copy_(t, non_blocking=True)
+    return host
+
+
+def _host_read(model, device):
+    """The ONE host round trip of a no-grad driver call (reference: one per look-ahead + 3 per step; ~75 us each on these boxes): the read of the
+    model's deferred numeric status synchronises the stream, which also completes whatever _to_pinned sent in front of it — so everything the
+    first push needs is enqueued BEFORE this, and after it only the rollout's own launches stand between the host and a busy GPU."""
+    copied = torch.cuda.Event()
+    copied.record(torch.cuda.current_stream(torch.device(device)))
+    model.take_status(device)
+    copied.synchronize()      # normally already complete (take_status synchronises the same stream); never rely on a subclass / stub doing so
 
 
 def _strict_status(model, device):
@@ -270,98 +296,71 @@ def _constants(bsz, n_obj, n_t, max_n, device):
     return c
 
 
+def _frames(obj, eef, dlt, n_his, obj_still):
+    """The inputs of a push's first model step: the cloud obj (B,n_obj,3) and the tool key-points eef (B,n_t,3) in each of the n_his history frames
+    -> state0 (B,n_his,N,3); no motion (obj_still, (B,n_obj,3) zeros) for the object rows and dlt (B,n_t,3) per step for the tool's -> delta (B,N,3).
+    One cat of expanded views each, for every driver: the differentiable ones record exactly this graph."""
+    bsz, n_obj, n_t = obj.shape[0], obj.shape[1], eef.shape[1]
+    state0 = torch.cat([obj[:, None].expand(bsz, n_his, n_obj, 3), eef[:, None].expand(bsz, n_his, n_t, 3)], dim=2)
+    return state0, torch.cat([obj_still, dlt], dim=1)
+
+
+def _push_inputs(task, obj, dec, theta, obj_still, order=None, shared=False):
+    """state0, delta and the gripper raise of one look-ahead push of dynamics(): the tool placed at the height of the cloud obj (B,n_obj,3) for the
+    decoded action rows dec (B,4) and angles theta (B,).
+    `shared`: every sample starts from the same cloud — its height is one reduction over n_obj values, not bsz of them (28 -> 5 us at 256 x 1 000).
+    `order`: the ragged rollout's — row r of everything per sample is sample order[r].  The action rows, theta and (unless shared: all rows are
+    one cloud) the previous frame are gathered HERE, in front of the tool placement: B n_obj 3 floats, where gathering the assembled state0 / delta
+    would move B H N 3."""
+    bsz = obj.shape[0]
+    if order is not None:
+        dec, theta = dec.index_select(0, order), theta.index_select(0, order)
+        obj = obj if shared else obj.index_select(0, order)
+    y = obj[0, :, 1].min().expand(bsz) if shared else obj[:, :, 1].min(dim=1).values
+    eef, dlt, raise_by = _place_tool_lean(task, dec, theta, y, obj.device, zero=obj_still[:, 0, 0])
+    return _frames(obj, eef, dlt, task["n_his"], obj_still) + (raise_by,)
+
+
 @torch.no_grad()
 def dynamics(state, action, model, device, ppm_optimizer, physics_param=None):
     task = ppm_optimizer.task_config
-    n_his, push_length = task["n_his"], task["push_length"]
     state = state.to(device, torch.float32)
     action = action.to(device, torch.float32)
     bsz, n_look = action.shape[0], action.shape[1]
-    decoded, repeat = decode_action(action, push_length=push_length)
+    decoded, repeat = decode_action(action, push_length=task["push_length"])
     n_obj, n_t = state.shape[0], ppm_optimizer.eef_num
-    N = n_obj + n_t
 
     attrs, p_instance, mask, tool_mask, obj_still = _constants(bsz, n_obj, n_t, task["max_n"], device)
     obj_still = obj_still.expand(bsz, n_obj, 3)
     phys = _physics(ppm_optimizer, physics_param, bsz, device)
+    src = ppm_optimizer.physics_param if physics_param is None else physics_param
+    same_phys = src[ppm_optimizer.material].dim() != 2      # one physics row for all samples: nothing to gather
     thr = threshold_sq(ppm_optimizer.adj_thresh, bsz, torch.device(device), _lib.AG_VARIANT_BATCH)
-    ragged = bool(getattr(model, "ragged_rollout", False))
-    rep_max = None if ragged else repeat.max(dim=0).values
     rep_cols = repeat.to(torch.int32).t().contiguous()      # (n_look, B): each look-ahead step's column contiguous, made before the sync
     seq = torch.zeros((bsz, n_look, n_obj, 3), device=device)
-
-    def prepare(li, obj, shared=False, order=None):        # tool key-points, history frames and per-step tool motion of look-ahead step li
-        # (`shared`: every sample starts from the same cloud — its height is one reduction over n_obj values, not bsz of them: 28 -> 5 us at 256 x 1 000)
-        # (`order`: the ragged rollout's — row r of everything per sample is sample order[r]; `obj` is given in that order already)
-        y = obj[0, :, 1].min().expand(bsz) if shared else obj[:, :, 1].min(dim=1).values
-        dec, theta = decoded[:, li], action[:, li, 2]
-        if order is not None:
-            dec, theta = dec.index_select(0, order), theta.index_select(0, order)
-        eef, dlt, raise_by = _place_tool_lean(task, dec, theta, y, device, zero=obj_still[:, 0, 0])
-        state0 = torch.cat([obj[:, None].expand(bsz, n_his, n_obj, 3), eef[:, None].expand(bsz, n_his, n_t, 3)], dim=2)
-        delta = torch.cat([obj_still, dlt], dim=1)
-        return state0, delta, raise_by
-
+    first = state[None].expand(bsz, n_obj, 3)
+    # model.ragged_rollout only changes a column's plan — (n_steps, order, active) of rollout().  Off: (the column's step maximum, None, None).
+    # On: every push is ONE ag_rollout_ragged call that computes a sample for exactly its own number of steps — the samples are ordered on the
+    # device (ag_rollout_order), what differs between samples is gathered into that order (attrs, p_instance and the masks are the same for every
+    # sample), and the library scatters each result back to its sample's row.  The per-step counts replace the step maximum in the one host read.
+    ragged = bool(getattr(model, "ragged_rollout", False))
     if ragged:
-        src = ppm_optimizer.physics_param if physics_param is None else physics_param
-        return _dynamics_ragged(model, device, task, state, phys, src[ppm_optimizer.material].dim() != 2, thr, rep_cols, seq, decoded, prepare,
-                                (attrs, p_instance, mask, tool_mask), n_t)
-    # everything the first look-ahead step needs is enqueued BEFORE the call's one host sync, so that after it only the rollout's own launches
-    # stand between the host and a busy GPU
-    ready = prepare(0, state[None].expand(bsz, n_obj, 3), shared=True)
-    # ONE host sync per call (reference: one per look-ahead + 3 per step): the step counts travel to pinned memory behind the set-up, and the read of
-    # the model's deferred numeric status — which synchronises the stream — completes both (one host round trip, ~75 us each on these boxes)
-    rep_host = _pinned(n_look, rep_max.dtype, device)
-    rep_host.copy_(rep_max, non_blocking=True)
-    copied = torch.cuda.Event()
-    copied.record(torch.cuda.current_stream(torch.device(device)))
-    model.take_status(device)
-    copied.synchronize()      # normally already complete (take_status synchronises the same stream); never rely on a subclass / stub doing so
-    max_steps = rep_host.tolist()
+        orders, counts = _ragged_plan(rep_cols, device)
+    ready = _push_inputs(task, first, decoded[:, 0], action[:, 0, 2], obj_still, orders[0] if ragged else None, shared=True)
+    if not ragged:      # the step maxima travel to pinned memory behind the first push's set-up, the last thing in front of the read
+        counts = _to_pinned(repeat.max(dim=0).values, device)
+    _host_read(model, device)
+    max_steps = None if ragged else counts.tolist()
     for li in range(n_look):
-        if li > 0:
-            ready = prepare(li, seq[:, li - 1])
+        rep = rep_cols[li]
+        n_steps, order, active = _push_plan(orders[li], counts[li], rep) if ragged else (max_steps[li], None, None)
+        if li > 0 or (ragged and order is None):      # (the first push's inputs stand ready, unless its plan fell back to the plain call's)
+            ready = _push_inputs(task, first if li == 0 else seq[:, li - 1], decoded[:, li], action[:, li, 2], obj_still, order, shared=li == 0)
         state0, delta, raise_by = ready
         direct = seq[:, 0] if n_look == 1 else None     # a single look-ahead step: the library writes the result tensor itself
-        res = rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr, rep_cols[li],
-                      max_steps[li], task["topk"], task["connect_tools_all"], n_t,
-                      _lib.AG_HEIGHT_MIN, None, raise_by, out=direct)
-        if direct is None:
-            seq[:, li] = res
-    _strict_status(model, device)
-    return {"state_seqs": seq, "action_seqs": decoded}
-
-
-def _dynamics_ragged(model, device, task, state, phys, same_phys, thr, rep_cols, seq, decoded, prepare, const, n_t):
-    """dynamics() with model.ragged_rollout: every look-ahead push as ONE ag_rollout_ragged call that computes a sample for exactly its own
-    number of steps.  Per column the samples are ordered on the device (ag_rollout_order) and everything that differs between samples — the
-    action rows, a per-sample physics table (`same_phys`: one row for all) and, behind the first push, the previous frame — is gathered into
-    that order; attrs, p_instance and the masks are the same for every sample.  The library scatters each result back to its sample's row.
-    Still ONE host read: the per-step counts replace the step maximum of the plain form in it."""
-    attrs, p_instance, mask, tool_mask = const
-    n_look, bsz = rep_cols.shape
-    n_obj = state.shape[0]
-    orders, act_host = _ragged_plan(rep_cols, device)
-    first = state[None].expand(bsz, n_obj, 3)
-    ready = prepare(0, first, shared=True, order=orders[0])
-    copied = torch.cuda.Event()
-    copied.record(torch.cuda.current_stream(torch.device(device)))
-    model.take_status(device)
-    copied.synchronize()
-    for li in range(n_look):
-        n_steps = _ragged_steps(act_host[li])
-        order = orders[li] if n_steps is not None else None
-        rep = rep_cols[li]
-        if order is None:      # a push longer than the ragged call takes: the plain call on the batch as it is (one more host read for its step count)
-            n_steps = int(rep.max())
-            ready = prepare(li, first if li == 0 else seq[:, li - 1], shared=li == 0)
-        elif li > 0:
-            ready = prepare(li, seq[:, li - 1].index_select(0, order), order=order)
-        state0, delta, raise_by = ready
-        direct = seq[:, 0] if n_look == 1 else None
         res = rollout(model, state0, delta, attrs, p_instance, phys if order is None or same_phys else phys.index_select(0, order), mask, tool_mask,
                       thr, rep if order is None else rep.index_select(0, order), n_steps, task["topk"], task["connect_tools_all"], n_t,
-                      _lib.AG_HEIGHT_MIN, None, raise_by, out=direct, order=order, active=None if order is None else act_host[li])
+                      _lib.AG_HEIGHT_MIN, None, raise_by, out=direct, order=order, active=active)
         if direct is None:
             seq[:, li] = res
     _strict_status(model, device)
@@ -382,9 +381,6 @@ def _frozen_view(model):
               non_rigid_predictor=NS(linear_0=lin(d.linear_0), linear_1=lin(d.linear_1), linear_2=lin(d.linear_2)))
 
 
-_LANES = {}
-
-
 def block_sum(x):
     """x (B, n) -> (B,): the sum over n in the ORDER of the rollout kernels' workgroup reduction (rollout_step_kernel, ag_step_update): 256
     strided per-thread partials, the xor butterfly 32, 16, .. 1 inside each of the four waves, then (w0 + w1) + (w2 + w3) — as tensor ops, so that
@@ -396,9 +392,7 @@ def block_sum(x):
     for j in range(k):
         acc = acc + x[:, j]
     v = acc.view(B, 4, 64)
-    lanes = _LANES.get(str(x.device))
-    if lanes is None:
-        lanes = _LANES[str(x.device)] = torch.arange(64, device=x.device)
+    lanes = _memo(_LANES, str(x.device), lambda: torch.arange(64, device=x.device))
     for o in (32, 16, 8, 4, 2, 1):
         v = v + v[..., lanes ^ o]
     w = v[..., 0]
@@ -461,26 +455,38 @@ def step_update(pred, states, delta, rec, repeat, ai, height_mode=_lib.AG_HEIGHT
     return _StepUpdate.apply(pred, states, delta, rec, repeat, ai, height_mode, obj_u8, raise_by)
 
 
-def _model_step(view, phys_key, consts, edges, repeat, ai, height, states, delta, phys, rec):
-    """One model step of the differentiable rollouts, shared by both drivers: the training forward on the step's edge lists, then the state update.
-    consts = (attrs, p_instance); edges = (csr, EdgeViews); height = (mode, obj_mask, raise_by, kernel) — kernel: step_update, else step_update_ops.
+def _model_step(view, phys_key, attrs, p_instance, csr, views, repeat, ai, height_mode, obj_mask, raise_by, kernel, states, delta, phys, rec):
+    """One model step of the differentiable rollouts: the training forward on the step's edge lists (csr and its EdgeViews), then the state update
+    — `kernel`: step_update's one launch each way, else the tensor ops of step_update_ops.
     A function of the four trailing tensors alone: under checkpoint_steps only they are kept, and this runs again in the backward pass."""
     from .train_model import TrainableDynamicsPredictor
-    attrs, p_instance = consts
-    csr, views = edges
-    mode, obj_mask, raise_by, kernel = height
     pred, _ = TrainableDynamicsPredictor.forward(view, states, attrs, csr, None, p_instance, action=delta, edge_views=views, **{phys_key: phys})
-    return (step_update if kernel else step_update_ops)(pred, states, delta, rec, repeat, ai, mode, obj_mask, raise_by)
+    return (step_update if kernel else step_update_ops)(pred, states, delta, rec, repeat, ai, height_mode, obj_mask, raise_by)
 
 
-def _run_step(checkpoint_steps, *args):
-    """_model_step, or — checkpoint_steps — the same graph whose saved activations are dropped and recomputed from the step's inputs when the
-    backward pass first asks for one.  The autograd graph is the same either way and every kernel is deterministic, so gradients keep their bits."""
-    if not checkpoint_steps:
-        return _model_step(*args)
+def _push_differentiable(view, ppm_optimizer, states, delta, attrs, p_instance, mask, tool_mask, phys, repeat, n_steps, checkpoint_steps=False,
+                         height_mode=_lib.AG_HEIGHT_MIN, obj_mask=None, raise_by=0.0, device_views=False, kernel=False):
+    """One push of the differentiable drivers, n_steps model steps on the detached weights `view` (_frozen_view) from states (B,H,N,3) -> the
+    record (B,n_obj,3) of every sample's step repeat[b].
+    Per step: the HIP edge builder under no_grad, `train_ops.EdgeViews` over its edges (device_views: both views in one launch), then _model_step.
+    checkpoint_steps: the same autograd graph, whose saved activations are dropped and recomputed from the step's four input tensors when the
+    backward pass first asks for one; every kernel is deterministic, so gradients keep their bits."""
     from functools import partial
     from torch.utils.checkpoint import checkpoint
-    return checkpoint(partial(_model_step, *args[:-4]), *args[-4:], use_reentrant=False, preserve_rng_state=False)
+    from . import graph, train_ops      # build_edges and EdgeViews are looked up at every call
+    task = ppm_optimizer.task_config
+    rec = torch.zeros((states.shape[0], p_instance.shape[1], 3), device=states.device)
+    for ai in range(1, 1 + n_steps):
+        with torch.no_grad():
+            csr = graph.build_edges(states[:, -1].detach(), ppm_optimizer.adj_thresh, mask, tool_mask, task["topk"], task["connect_tools_all"],
+                                    "batch", max_tools=ppm_optimizer.eef_num)
+        step = partial(_model_step, view, ppm_optimizer.material + "_physics_param", attrs, p_instance, csr,
+                       train_ops.EdgeViews(csr, device_views=device_views), repeat, ai, height_mode, obj_mask, raise_by, kernel)
+        if checkpoint_steps:
+            states, rec = checkpoint(step, states, delta, phys, rec, use_reentrant=False, preserve_rng_state=False)
+        else:
+            states, rec = step(states, delta, phys, rec)
+    return rec
 
 
 def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics_param=None, checkpoint_steps=False):
@@ -500,21 +506,15 @@ def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics
     then ag_step_update's one launch each way instead of the tensor ops (step_update_ops), whose values and gradients it reproduces bit for
     bit (tests/test_sysid_grad.py) — except where two particles share the minimum height exactly: the kernel sends the height's gradient to
     the first of them, torch.min to the one it returned."""
-    from .graph import build_edges
-    from .train_ops import EdgeViews
-
     task = ppm_optimizer.task_config
-    n_his, push_length, ratio = task["n_his"], task["push_length"], task["sim_real_ratio"]
     state = state.to(device, torch.float32)
     action = action.to(device, torch.float32)
     bsz, n_look = action.shape[0], action.shape[1]
-    decoded, repeat = decode_action(action, push_length=push_length)
+    decoded, repeat = decode_action(action, push_length=task["push_length"])
     n_obj, n_t = state.shape[0], ppm_optimizer.eef_num
     attrs, p_instance, mask, tool_mask, _ = _constants(bsz, n_obj, n_t, task["max_n"], device)
     phys = _physics(ppm_optimizer, physics_param, bsz, device)
-    phys_key = ppm_optimizer.material + "_physics_param"
     view = _frozen_view(model)
-    raise_by = 0.01 * ratio if task["gripper_enable"] else 0.0
     obj_still = torch.zeros((bsz, n_obj, 3), device=device)
     max_steps = repeat.max(dim=0).values.tolist()
     rep_cols = repeat.t().contiguous()      # (n_look, B) int32: a look-ahead step's column contiguous, as ag_step_update reads it
@@ -524,18 +524,37 @@ def dynamics_differentiable(state, action, model, device, ppm_optimizer, physics
         if li > 0:
             obj = seqs[li - 1].detach()                                               # forward_dynamics.py:38
         y = obj[:, :, 1].min(dim=1).values
-        eef, dlt, _ = _place_tool(task, decoded[:, li], action[:, li, 2], y, device)
-        states = torch.cat([obj[:, None].expand(bsz, n_his, n_obj, 3), eef[:, None].expand(bsz, n_his, n_t, 3)], dim=2)
-        delta = torch.cat([obj_still, dlt], dim=1)
-        rec = torch.zeros((bsz, n_obj, 3), device=device)
-        for ai in range(1, 1 + int(max_steps[li])):
-            with torch.no_grad():
-                csr = build_edges(states[:, -1].detach(), ppm_optimizer.adj_thresh, mask, tool_mask, task["topk"], task["connect_tools_all"],
-                                  "batch", max_tools=n_t)
-            states, rec = _run_step(checkpoint_steps, view, phys_key, (attrs, p_instance), (csr, EdgeViews(csr)), rep_cols[li], ai,
-                                    (_lib.AG_HEIGHT_MIN, None, raise_by, bool(checkpoint_steps)), states, delta, phys, rec)
-        seqs.append(rec)
+        eef, dlt, raise_by = _place_tool(task, decoded[:, li], action[:, li, 2], y, device)
+        states, delta = _frames(obj, eef, dlt, task["n_his"], obj_still)
+        seqs.append(_push_differentiable(view, ppm_optimizer, states, delta, attrs, p_instance, mask, tool_mask, phys, rep_cols[li],
+                                         int(max_steps[li]), checkpoint_steps, raise_by=raise_by, kernel=bool(checkpoint_steps)))
     return {"state_seqs": torch.stack(seqs, dim=1), "action_seqs": decoded}
+
+
+def _masked_inputs(state_mask, n_t, max_n):
+    """What the masked drivers derive from state_mask (B,n_obj) — bool or 0/1, on its device — for n_t tool slots behind the n_obj object slots and
+    max_n instances -> attrs (B,N,2), p_instance (B,n_obj,max_n) in its "first `count` slots" form (forward_dynamics.py:292-300), mask and
+    tool_mask (B,N) bool, obj_mask (B,n_obj) bool, cnt (B,) the valid slots per sample.  ONE statement of it: the gradient sys-id is tested
+    against the no-grad one, so both must see the same bits."""
+    bsz, n_obj = state_mask.shape
+    device, N = state_mask.device, n_obj + n_t
+    obj_mask = state_mask.bool()
+    cnt = state_mask.sum(dim=1)
+    attrs = torch.zeros((bsz, N, 2), device=device)
+    attrs[:, :n_obj, 0] = state_mask.float()
+    attrs[:, n_obj:, 1] = 1.0
+    p_instance = torch.zeros((bsz, n_obj, max_n), device=device)
+    p_instance[:, :, 0] = (torch.arange(n_obj, device=device)[None] < cnt[:, None]).float()
+    mask = torch.ones((bsz, N), dtype=torch.bool, device=device)
+    mask[:, :n_obj] = obj_mask
+    tool_mask = torch.zeros((bsz, N), dtype=torch.bool, device=device)
+    tool_mask[:, n_obj:] = True
+    return attrs, p_instance, mask, tool_mask, obj_mask, cnt
+
+
+def _masked_height(state, state_mask, cnt):
+    """The masked mean of y over a sample's valid slots (forward_dynamics.py:235): where the masked drivers put the tool at the start."""
+    return (state[:, :, 1] * state_mask).sum(dim=1) / cnt
 
 
 def dynamics_masked_differentiable(state_init, state_mask, action, model, device, ppm_optimizer, physics_param=None, checkpoint_steps=False):
@@ -548,97 +567,52 @@ def dynamics_masked_differentiable(state_init, state_mask, action, model, device
     Per model step: the HIP edge builder under no_grad, both views of its edge list on the device (EdgeViews(device_views=True): one launch
     of ag_edge_views), TrainableDynamicsPredictor.forward, and the state update in one launch each way (ag_step_update_forward / _backward).
     One host read per model step (the edge count) plus one for the step count.  checkpoint_steps: as in `dynamics_differentiable`."""
-    from .graph import build_edges
-    from .train_ops import EdgeViews
-
     task = ppm_optimizer.task_config
-    n_his, push_length = task["n_his"], task["push_length"]
     state_mask = state_mask.to(device)
-    obj_mask = state_mask.bool()
+    n_t = ppm_optimizer.eef_num
+    attrs, p_instance, mask, tool_mask, obj_mask, cnt = _masked_inputs(state_mask, n_t, task["max_n"])
     state = state_init.to(device, torch.float32)
     state = torch.where(obj_mask[:, :, None], state, state.detach())      # masked-out rows carry their values along, never a gradient
     action = action.to(device, torch.float32)
     bsz, n_obj = state.shape[0], state.shape[1]
-    decoded, repeat = decode_action(action[:, None], push_length=push_length)
+    decoded, repeat = decode_action(action[:, None], push_length=task["push_length"])
     decoded, repeat = decoded[:, 0], repeat[:, 0].contiguous()
-    n_t = ppm_optimizer.eef_num
-    N = n_obj + n_t
-
-    cnt = state_mask.sum(dim=1)
-    y = (state[:, :, 1] * state_mask).sum(dim=1) / cnt                            # forward_dynamics.py:235
-    eef, dlt, raise_by = _place_tool(task, decoded, action[:, 2], y, device)
-    states = torch.cat([state[:, None].expand(bsz, n_his, n_obj, 3), eef[:, None].expand(bsz, n_his, n_t, 3)], dim=2)
-    delta = torch.cat([torch.zeros((bsz, n_obj, 3), device=device), dlt], dim=1)
-    attrs = torch.zeros((bsz, N, 2), device=device)
-    attrs[:, :n_obj, 0] = state_mask.float()
-    attrs[:, n_obj:, 1] = 1.0
-    p_instance = torch.zeros((bsz, n_obj, task["max_n"]), device=device)           # first `count` slots, :292-300
-    p_instance[:, :, 0] = (torch.arange(n_obj, device=device)[None] < cnt[:, None]).float()
-    mask = torch.ones((bsz, N), dtype=torch.bool, device=device)
-    mask[:, :n_obj] = obj_mask
-    tool_mask = torch.zeros((bsz, N), dtype=torch.bool, device=device)
-    tool_mask[:, n_obj:] = True
+    eef, dlt, raise_by = _place_tool(task, decoded, action[:, 2], _masked_height(state, state_mask, cnt), device)
+    states, delta = _frames(state, eef, dlt, task["n_his"], torch.zeros((bsz, n_obj, 3), device=device))
     phys = _physics(ppm_optimizer, physics_param, bsz, device)
-    phys_key = ppm_optimizer.material + "_physics_param"
-    view = _frozen_view(model)
-    rec = torch.zeros((bsz, n_obj, 3), device=device)
-    for ai in range(1, 1 + int(repeat.max().item())):
-        with torch.no_grad():
-            csr = build_edges(states[:, -1].detach(), ppm_optimizer.adj_thresh, mask, tool_mask, task["topk"], task["connect_tools_all"],
-                              "batch", max_tools=n_t)
-        states, rec = _run_step(checkpoint_steps, view, phys_key, (attrs, p_instance), (csr, EdgeViews(csr, device_views=True)), repeat, ai,
-                                (_lib.AG_HEIGHT_MASKED_MEAN, obj_mask, raise_by, True), states, delta, phys, rec)
+    rec = _push_differentiable(_frozen_view(model), ppm_optimizer, states, delta, attrs, p_instance, mask, tool_mask, phys, repeat, int(repeat.max().item()),
+                               checkpoint_steps, height_mode=_lib.AG_HEIGHT_MASKED_MEAN, obj_mask=obj_mask, raise_by=raise_by, device_views=True,
+                               kernel=True)
     return {"state_seqs": rec, "action_seqs": decoded}
 
 
 @torch.no_grad()
 def dynamics_masked(state_init, state_mask, action, model, device, ppm_optimizer, physics_param=None):
     task = ppm_optimizer.task_config
-    n_his, push_length = task["n_his"], task["push_length"]
     state = state_init.to(device, torch.float32)
     state_mask = state_mask.to(device)
     action = action.to(device, torch.float32)
     bsz, n_obj = state.shape[0], state.shape[1]
-    decoded, repeat = decode_action(action[:, None], push_length=push_length)
+    decoded, repeat = decode_action(action[:, None], push_length=task["push_length"])
     decoded, repeat = decoded[:, 0], repeat[:, 0]
     n_t = ppm_optimizer.eef_num
-    N = n_obj + n_t
 
-    cnt = state_mask.sum(dim=1)
-    y = (state[:, :, 1] * state_mask).sum(dim=1) / cnt                            # forward_dynamics.py:235
-    eef, dlt, raise_by = _place_tool(task, decoded, action[:, 2], y, device)
-    state0 = torch.empty((bsz, n_his, N, 3), device=device)
-    state0[:, :, :n_obj] = state[:, None]
-    state0[:, :, n_obj:] = eef[:, None]
-    delta = torch.zeros((bsz, N, 3), device=device)
-    delta[:, n_obj:] = dlt
-    attrs = torch.zeros((bsz, N, 2), device=device)
-    attrs[:, :n_obj, 0] = state_mask.float()
-    attrs[:, n_obj:, 1] = 1.0
-    p_instance = torch.zeros((bsz, n_obj, task["max_n"]), device=device)           # first `count` slots, :292-300
-    p_instance[:, :, 0] = (torch.arange(n_obj, device=device)[None] < cnt[:, None]).float()
-    mask = torch.ones((bsz, N), dtype=torch.bool, device=device)
-    mask[:, :n_obj] = state_mask.bool()
-    tool_mask = torch.zeros((bsz, N), dtype=torch.bool, device=device)
-    tool_mask[:, n_obj:] = True
+    attrs, p_instance, mask, tool_mask, obj_mask, cnt = _masked_inputs(state_mask, n_t, task["max_n"])
+    obj_still = torch.zeros((bsz, n_obj, 3), device=device)
+    eef, dlt, raise_by = _place_tool_lean(task, decoded, action[:, 2], _masked_height(state, state_mask, cnt), device, zero=obj_still[:, 0, 0])
+    state0, delta = _frames(state, eef, dlt, task["n_his"], obj_still)
     phys = _physics(ppm_optimizer, physics_param, bsz, device)
     thr = threshold_sq(ppm_optimizer.adj_thresh, bsz, torch.device(device), _lib.AG_VARIANT_BATCH)
-    obj_mask, order, active = state_mask.bool(), None, None
-    n_steps = None
-    if getattr(model, "ragged_rollout", False):      # the per-step counts instead of the step maximum, in the same one host read
-        orders, act_host = _ragged_plan(repeat.to(torch.int32)[None].contiguous(), device)
-        copied = torch.cuda.Event()
-        copied.record(torch.cuda.current_stream(torch.device(device)))
-        model.take_status(device)
-        copied.synchronize()
-        n_steps = _ragged_steps(act_host[0])
-        if n_steps is not None:      # every per-sample input in the order of the call; the library scatters the result back
-            order, active = orders[0], act_host[0]
-            state0, delta, attrs, p_instance, mask, tool_mask, phys, repeat, obj_mask = (
-                t.index_select(0, order) for t in (state0, delta, attrs, p_instance, mask, tool_mask, phys, repeat, obj_mask))
-    if n_steps is None:
-        n_steps = int(repeat.max().item())
-        model.take_status(device)
+    ragged = bool(getattr(model, "ragged_rollout", False))      # the per-step counts instead of the step maximum, in the same one host read
+    if ragged:
+        orders, counts = _ragged_plan(repeat.to(torch.int32)[None].contiguous(), device)
+    else:
+        counts = _to_pinned(repeat.max(), device)
+    _host_read(model, device)
+    n_steps, order, active = _push_plan(orders[0], counts[0], repeat) if ragged else (int(counts.tolist()), None, None)
+    if order is not None:      # every per-sample input, built already, in the order of the call; the library scatters the result back
+        state0, delta, attrs, p_instance, mask, tool_mask, phys, repeat, obj_mask = (
+            t.index_select(0, order) for t in (state0, delta, attrs, p_instance, mask, tool_mask, phys, repeat, obj_mask))
     seq = rollout(model, state0, delta, attrs, p_instance, phys, mask, tool_mask, thr, repeat, n_steps, task["topk"],
                   task["connect_tools_all"], n_t, _lib.AG_HEIGHT_MASKED_MEAN, obj_mask, raise_by, order=order, active=active)
     _strict_status(model, device)

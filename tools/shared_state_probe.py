@@ -21,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from adaptigraph_amd import _lib, configs, synth                               # noqa: E402
-from adaptigraph_amd.forward_dynamics import _place_tool_lean, _constants, rollout   # noqa: E402
+from adaptigraph_amd.forward_dynamics import _constants, _frames, _place_tool_lean, rollout   # noqa: E402
 from adaptigraph_amd.graph import threshold_sq                                 # noqa: E402
 from adaptigraph_amd.model import DynamicsPredictor                            # noqa: E402
 from adaptigraph_amd.plan_utils import decode_action                           # noqa: E402
@@ -59,8 +59,7 @@ def main():
     obj = state[None].expand(B, n_obj, 3)
 
     def run(eef_, t, mask_=None):
-        state0 = torch.cat([obj[:, None].expand(B, n_his, n_obj, 3), eef_[:, None].expand(B, n_his, n_t, 3)], dim=2).contiguous()
-        delta = torch.cat([obj_still, dlt], dim=1).contiguous()
+        state0, delta = _frames(obj, eef_, dlt, n_his, obj_still)
         rep = torch.full((B,), t, dtype=torch.int32, device=dev)
         _, fin = rollout(model, state0, delta, attrs, p_instance, phys, mask if mask_ is None else mask_, tool_mask, thr, rep, t, mm["topk"], mm["connect_tools_all"], n_t,
                          _lib.AG_HEIGHT_MIN, None, raise_by, return_state=True)
