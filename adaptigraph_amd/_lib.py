@@ -144,6 +144,10 @@ SIGNATURES = {
     "ag_sim_box_push": (c_int, [c_void_p] * 13 + [c_int] * 8 + [c_float] * 9 + [c_void_p]),
     # simulated depth cameras
     "ag_render_depth": (c_int, [c_void_p] * 6 + [c_int] * 5 + [c_void_p] * 3),
+    # rollout and planning records drawn as images
+    "ag_draw_scratch_bytes": (c_size_t, [c_int] * 2),
+    "ag_draw": (c_int, [c_void_p, c_int] * 4 + [c_void_p, c_int, P(c_double)] + [c_int] * 4 + [c_void_p, c_int] * 2 + [c_int] * 2
+                + [c_void_p, c_size_t, c_void_p, c_void_p]),
     # training batches assembled on the device
     "ag_gather_clouds": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3),
     "ag_assemble_batch": (c_int, [P(BatchDims)] + [c_void_p] * 8 + [P(BatchOut), c_void_p]),

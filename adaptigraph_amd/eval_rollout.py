@@ -1,6 +1,6 @@
 """Open-loop evaluation rollouts over a recorded dataset on the engine — SURVEY.md §8f row n3.
 
-Mirrors src/dynamics/rollout/rollout.py (:20-319, minus image/video output) and the graph set-up of
+Mirrors src/dynamics/rollout/rollout.py (:20-319; its per-step images as numbered PNGs drawn by viz.py, no video) and the graph set-up of
 src/dynamics/rollout/graph.py:233-399.  The reference rolls ONE start graph at a time, rebuilding dense Rr/Rs on the host
 and copying state back and forth every step.  Which frames a rollout visits depends only on the frame-pair table, never on
 the predictions, so here the frame schedule of every start graph is resolved on the host up front (`frame_schedule`), the
@@ -132,13 +132,26 @@ def frame_schedule(pairs, n_his, n_frames, current_start, current_end, next_fn, 
     return sched
 
 
+def _viz_options(config_or_none, dirs):
+    """What rollout_batch's `viz` takes: the directory of every rollout's images, and from rollout_config the optional `viz_size` (H, W) and
+    `viz_radius` (the particles' radius in simulator units; default: the material's simulator default)."""
+    rc = (config_or_none or {}).get("rollout_config", {})
+    return {"dirs": list(dirs), "size": tuple(rc.get("viz_size", (720, 1280))), "radius": rc.get("viz_radius")}
+
+
 @torch.no_grad()
-def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list, obj_pos_list, dataset_config, scripted=False):
+def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list, obj_pos_list, dataset_config, viz=None, scripted=False):
     """Advance B start graphs together.  graphs[b] from construct_graph, schedules[b] from frame_schedule, eef_pos_list[b]
     (T,N_eef,3) / obj_pos_list[b] (T,N_obj_all,3) the episode the graph came from.  -> [error list per graph]; entry t is
     the mean key-point distance to the ground truth of frame schedules[b][t][1].
     `scripted`: the step loop as ONE `ag_rollout_scripted` call (forward_dynamics.rollout_scripted) — the same predictions bit for bit, the
-    error reduced by its kernel in a fixed order (equal to the loop's up to the rounding of an fp32 sum), no launch-by-launch host work."""
+    error reduced by its kernel in a fixed order (equal to the loop's up to the rounding of an fp32 sum), no launch-by-launch host work.
+    `viz`: _viz_options(...) -- every step of rollout b is drawn into viz["dirs"][b] as {start:06}_{end:06}_{pred,gt,both}.png (the reference's
+    names, graph.py:163-225, with png for jpg) by viz.write_rollout_record.  As in rollout.py:40-57, :140-146 the picture of step t shows the
+    graph that step t's forward READS, everything at frame `start`: the key points of state[:, -1] (the start graph's for t = 0, then the
+    prediction of step t - 1), the recorded key points and particles of frame `start`, the tool at `start`, and the edges built from exactly
+    those points.  The states come from what this call computes anyway (the scripted path: its recorded predictions); drawing reads and
+    never perturbs, so the errors are those of viz=None."""
     P = _dataset_params(dataset_config)
     dev = torch.device(device)
     B, max_nobj = len(graphs), P["max_nobj"]
@@ -147,14 +160,26 @@ def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list,
     gt = np.zeros((B, T, max_nobj, 3), np.float32)
     eef_start = np.zeros((B, T, n_eef, 3), np.float32)
     eef_delta = np.zeros((B, T, n_eef, 3), np.float32)
+    gt_start = np.zeros((B, T, max_nobj, 3), np.float32) if viz is not None else None      # the recorded key points at frame `start`: drawn only
     for b, sched in enumerate(schedules):
         for t, (s, e) in enumerate(sched):
             kp = np.asarray(obj_pos_list[b][e])[fps_idx_lists[b]]
             gt[b, t, :len(kp)] = kp
+            if viz is not None:
+                gt_start[b, t, :len(kp)] = np.asarray(obj_pos_list[b][s])[fps_idx_lists[b]]
             eef_start[b, t] = eef_pos_list[b][s]
             eef_delta[b, t] = np.asarray(eef_pos_list[b][e]) - np.asarray(eef_pos_list[b][s])
     gt, eef_start, eef_delta = (torch.from_numpy(a).to(dev) for a in (gt, eef_start, eef_delta))
     stack = lambda k: torch.stack([g[k].to(dev) for g in graphs], 0)
+
+    def draw(read_states, edges):
+        """read_states[t] (B, N, 3): the last frame of the history step t's forward read; edges[t]: the graph built from it."""
+        from . import viz as vz
+        vz.write_rollout_record(viz["dirs"], schedules, torch.stack([x[:, :max_nobj] for x in read_states], 1), torch.from_numpy(gt_start).to(dev),
+                                eef_start, edges, [len(f) for f in fps_idx_lists], max_nobj,
+                                [[np.asarray(obj_pos_list[b][s]) for s, _ in sched] for b, sched in enumerate(schedules)],
+                                dataset_config["materials"][0], dev, radius=viz["radius"], H=viz["size"][0], W=viz["size"][1])
+
     state, action, attrs, p_instance = stack("state").float(), stack("action").float(), stack("attrs"), stack("p_instance")
     state_mask, eef_mask, obj_mask = stack("state_mask"), stack("eef_mask"), stack("obj_mask")
     phys_key = [k for k in graphs[0] if k.endswith("_physics_param")]
@@ -163,16 +188,24 @@ def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list,
     if scripted:
         from .forward_dynamics import rollout_scripted
         thr = threshold_sq(P["adj_thresh"], B, dev, AG_VARIANT_SINGLE)
-        errors = rollout_scripted(model, state, action, eef_start, eef_delta, attrs, p_instance, phys[phys_key[0]], state_mask, eef_mask, thr,
-                                  P["topk"], P["connect_tool_all"], n_eef, variant="single", gt=gt, obj_mask=obj_mask,
-                                  return_pred=False)["err"].cpu().numpy()
+        out = rollout_scripted(model, state, action, eef_start, eef_delta, attrs, p_instance, phys[phys_key[0]], state_mask, eef_mask, thr,
+                               P["topk"], P["connect_tool_all"], n_eef, variant="single", gt=gt, obj_mask=obj_mask, return_pred=viz is not None)
+        errors = out["err"].cpu().numpy()
+        if viz is not None:      # the graph of step t, rebuilt from the recorded predictions: state0's last frame, then (prediction t - 1, tool of step t)
+            last = [state[:, -1]] + [torch.cat([out["pred_seq"][:, t - 1], eef_start[:, t]], 1) for t in range(1, T)]
+            draw(last, [build_edges(x, P["adj_thresh"], state_mask, eef_mask, P["topk"], P["connect_tool_all"], "single", max_tools=n_eef)
+                        for x in last])
         return [[errors[b, t] for t in range(len(schedules[b]))] for b in range(B)]
     n_valid = obj_mask.sum(1).clamp_min(1).float()
     errors = torch.zeros((B, T), device=dev)
+    read_states, graphs_seen = [], []
     for t in range(T):
         # step 0 uses the start graph's own state/action; its edges are rebuilt here (same states -> same edges as graph['Rr'])
         edges = build_edges(state[:, -1], P["adj_thresh"], state_mask, eef_mask, P["topk"], P["connect_tool_all"], "single",
                             max_tools=n_eef)
+        if viz is not None:
+            read_states.append(state[:, -1])
+            graphs_seen.append(edges)
         pred, _ = model(state, attrs, edges, None, p_instance, action=action, **phys)
         errors[:, t] = ((pred - gt[:, t]).norm(dim=-1) * obj_mask).sum(1) / n_valid
         if t + 1 < T:
@@ -181,17 +214,21 @@ def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list,
             action = torch.zeros_like(action)
             action[:, max_nobj:] = eef_delta[:, t + 1]
     errors = errors.cpu().numpy()
+    if viz is not None:
+        draw(read_states, graphs_seen)
     return [[errors[b, t] for t in range(len(schedules[b]))] for b in range(B)]
 
 
 def rollout_from_start_graph(graph, fps_idx_list, dataset_config, material_config, model, device, eef_pos, obj_pos,
                              current_start, current_end, get_next_pair_or_break_func, pairs, save_dir=None, viz=False,
                              imgs=None, cam_info=None, scripted=False):
-    """Reference signature (rollout.py:20-143) for one start graph; `viz` output is not produced by this engine.  `scripted`: see rollout_batch."""
+    """Reference signature (rollout.py:20-143) for one start graph.  `viz` (with `save_dir`) writes every step's images there, over the sphere
+    splat of the recorded particles: `imgs` and `cam_info` are not read.  `scripted`: see rollout_batch."""
     n_his = dataset_config["n_his"]
     assert eef_pos.shape[0] == obj_pos.shape[0]
     sched = frame_schedule(pairs, n_his, obj_pos.shape[0], current_start, current_end, get_next_pair_or_break_func)
-    return rollout_batch(model, device, [graph], [fps_idx_list], [sched], [eef_pos], [obj_pos], dataset_config, scripted=scripted)[0]
+    return rollout_batch(model, device, [graph], [fps_idx_list], [sched], [eef_pos], [obj_pos], dataset_config,
+                         viz=_viz_options(None, [save_dir]) if viz and save_dir is not None else None, scripted=scripted)[0]
 
 
 def _episode_first_pairs(dataset_config, episode_idx):
@@ -218,10 +255,12 @@ def _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_i
 
 def rollout_episode_pushes(model, device, dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param,
                            save_dir, viz=False, imgs=None, cam_info=None, fps_device=None, scripted=False):
-    """-> [error list per push]; writes error_<i>.txt per push like the reference (rollout.py:145-196; no plots/videos)."""
+    """-> [error list per push]; writes error_<i>.txt per push like the reference (rollout.py:145-196; no plots/videos) and, with `viz`, every
+    step's images beside them."""
     starts = _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param, device,
                              fps_device=fps_device)
-    errs = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config, scripted=scripted) if starts else []
+    errs = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config, viz=_viz_options(None, [save_dir] * len(starts)) if viz else None,
+                         scripted=scripted) if starts else []
     for i, e in enumerate(errs):
         np.savetxt(os.path.join(save_dir, f"error_{i + 1}.txt"), np.array(e))
     return errs
@@ -232,7 +271,8 @@ def rollout_dataset(model, device, config, save_dir, viz=False, fps_device=None,
     rollout), rollout.py:198-265.  All pushes of all episodes run as ONE batch.  -> step_error array.
     `fps_device`: the key-point sampling of EVERY start graph runs there as one `fps_batch` call (one launch per pass for the whole split).
     Building a start graph draws nothing but its sampling's numbers from the RNG, so the draws come in the same order and the start graphs
-    are the same as with the per-graph host sampling.  `scripted`: see rollout_batch."""
+    are the same as with the per-graph host sampling.  `scripted`: see rollout_batch.  `viz`: every step of every push is drawn beside its
+    error file (see rollout_batch)."""
     dataset_config, material_config = config["dataset_config"], config["material_config"]
     pair_lists, physics_params = load_dataset(dataset_config, material_config, phase="valid")
     pair_lists = np.array(pair_lists)
@@ -253,10 +293,13 @@ def rollout_dataset(model, device, config, save_dir, viz=False, fps_device=None,
                               device, fps_idx_lists=fps_idx.get(episode_idx))
         starts.extend(epi)
         owners.extend((episode_idx, i + 1) for i in range(len(epi)))
-    total = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config, scripted=scripted)
+    push_dir = lambda episode_idx: os.path.join(save_dir, f"{episode_idx}", "short")      # noqa: E731
+    for episode_idx, _ in owners:
+        os.makedirs(push_dir(episode_idx), exist_ok=True)
+    total = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config,
+                          viz=_viz_options(config, [push_dir(e) for e, _ in owners]) if viz else None, scripted=scripted)
     for (episode_idx, push), e in zip(owners, total):
-        d = os.path.join(save_dir, f"{episode_idx}", "short")
-        os.makedirs(d, exist_ok=True)
+        d = push_dir(episode_idx)
         np.savetxt(os.path.join(d, f"error_{push}.txt"), np.array(e))
     min_step = min(len(e) for e in total)
     step_error = np.array([[e[i] for e in total] for i in range(min_step)], np.float64)

@@ -1,7 +1,7 @@
 """Simulated depth cameras: depth and id images of a particle scene from calibrated pinhole cameras, every particle a sphere, the table a plane
 (DESIGN.md §8.14).  It is what the reference takes from its simulator's renderer (`pyflex.render(render_depth=True)`, flex_env.py:151-189,
-:404-409), for the project's own simulators (sim/): a sphere splat of their particles, NOT FleX's renderer, with no tool, no colour and no
-sensor noise.
+:404-409), for the project's own simulators (sim/): a sphere splat of their particles, NOT FleX's renderer, with no tool and no sensor
+noise; colour images are viz.py's, from the id image.
 
 Two paths, one result.  `render_depth_host` is the statement of the arithmetic, in numpy; `render_depth(..., device=)` is one launch of
 csrc/ag_render.hip and returns the same bits.  All of it is float64 on float32 inputs, every product and sum rounded on its own in the written

@@ -96,16 +96,42 @@ class SimEnv:
                                                   self.near, self.far)
         else:
             depth, ids = self._renderer.launch(pts.contiguous(), self._n_dev, self._radius_dev)
+        self.last_ids = ids[0]      # what the cameras saw last: the closed loop's pictures are drawn over it
         return depth[0], ids[0]
+
+    def color(self, ids):
+        """The colour images of id images `ids` (C, H, W) as `render` returns them -> (C, H, W, 4) uint8 RGBA: viz.draw with an empty display
+        list over background mode 2, every particle viz.PALETTE[id % 4], the table and the void viz.TABLE_COLOR and viz.VOID_COLOR.  The
+        device path is one ag_draw call into the environment's own canvas, which the next call overwrites."""
+        from . import viz
+        C = len(self.R_list)
+        frames = np.array([[c, 0, 0, c] for c in range(C)], np.int32)
+        if self.device is None:
+            return viz.draw_host(np.zeros((0, 3), np.float32), np.zeros((0, 4), np.int32), np.zeros((0, 4), np.int32), frames,
+                                 render.camera_rows(self.R_list, self.t_list, self.intr_list), self.H, self.W, 256, 2, ids, viz.PALETTE,
+                                 viz.TABLE_COLOR, viz.VOID_COLOR, self.near)
+        import torch
+        if getattr(self, "_canvas", None) is None:
+            self._canvas = viz.DeviceCanvas(render.camera_rows(self.R_list, self.t_list, self.intr_list), self.H, self.W, C, 1, self.near, self.device)
+            self._frames = torch.from_numpy(frames).to(self.device)
+            self._palette = torch.tensor(viz.PALETTE, dtype=torch.int32, device=self.device)
+            self._no_pts = torch.zeros((0, 3), dtype=torch.float32, device=self.device)
+            self._no_rows = torch.zeros((0, 4), dtype=torch.int32, device=self.device)
+        return self._canvas.launch(self._no_pts, self._no_rows, self._no_rows, self._frames, 256, 2, ids.contiguous(), self._palette,
+                                   viz.TABLE_COLOR, viz.VOID_COLOR)
 
     def get_obs(self, get_color=False, get_depth=True):
         """{"depth_i": (1, H, W) float32 in metres, "mask_i": (1, H, W) bool = the pixel shows a particle} per camera i (real_env.py:152-198 with
-        one observation step; no colour is rendered).  The mask is what the reference gets from its detection and segmentation models."""
-        if get_color:
-            raise ValueError("SimEnv renders no colour images")
+        one observation step) and, with `get_color`, "color_i": (1, H, W, 3) uint8, the sphere splat in `color`'s colours.  The mask is what the
+        reference gets from its detection and segmentation models."""
         obs = {}
-        if get_depth:
+        if get_depth or get_color:
             depth, ids = self.render()
+        if get_color:
+            rgba = self.color(ids)
+            for i in range(len(self.R_list)):
+                obs[f"color_{i}"] = rgba[i][None, :, :, :3]
+        if get_depth:
             for i in range(len(self.R_list)):
                 obs[f"depth_{i}"] = depth[i][None]
                 obs[f"mask_{i}"] = (ids[i] >= 0)[None]

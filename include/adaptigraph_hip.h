@@ -611,7 +611,7 @@ int ag_sim_box_push(const int32_t *n, const float *q, const float *m, const floa
                     float eps, float v_rest, float cap, float lift, ag_stream_t stream);
 
 /* ---- simulated depth cameras (what the reference takes from its simulator's renderer, src/sim/sim_env/flex_env.py:151-189, :404-409): depth and
- * id images of E particle scenes from C calibrated pinhole cameras in ONE launch, every particle a sphere, the table a plane.  No tool, no colour,
+ * id images of E particle scenes from C calibrated pinhole cameras in ONE launch, every particle a sphere, the table a plane.  No tool (colour: ag_draw),
  * no sensor noise.  The arithmetic is stated by adaptigraph_amd/render.py:render_depth_host and repeated here operation for
  * operation -- float64 on float32 inputs, products and sums rounded separately, only + - * / sqrt -- so the kernel gives the statement's bits.
  * DEVICE arrays: pts (E,n_max,3) fp32 sphere centres in the cameras' world frame; n (E) int32 spheres per episode (an n outside 0 .. n_max renders
@@ -635,6 +635,38 @@ int ag_sim_box_push(const int32_t *n, const float *q, const float *m, const floa
 #define AG_RENDER_MAX_PARTICLES 4096
 int ag_render_depth(const float *pts, const int32_t *n, const float *radius, const double *cams, const double *plane, const double *limits, int E,
                     int n_max, int C, int H, int W, float *depth, int32_t *id, ag_stream_t stream);
+
+/* ---- rollout and planning records drawn as images (what the reference draws with cv2: src/dynamics/rollout/graph.py:44-230 `visualize_graph`,
+ * src/planning/plan_utils.py:104-300 `visualize_img`): F frames of H x W RGBA pixels from a display list -- discs and thick segments between
+ * projected points, in paint order over a background -- in TWO launches.  The arithmetic is stated by
+ * adaptigraph_amd/viz.py:draw_host and repeated here operation for operation, so the kernel gives the statement's bits.  Our coverage rule, not
+ * cv2's Bresenham lines or its anti-aliasing; no text; spheres for particles (the background of mode 2 is ag_render_depth's id image).
+ * DEVICE arrays: pts (n_pts,3) fp32 points in the cameras' world frame; prims (n_prim,4) int32 = point a, point b, style, 0; styles (n_style,4)
+ * int32 = kind (0 disc about a, 1 segment a -> b), size (disc radius / segment width in pixels, 0 .. AG_DRAW_MAX_SIZE), layer (0 opaque,
+ * 1 overlay), colour 0xRRGGBB; frames (F,4) int32 = camera, first primitive, primitive count, background index; cams (C,25) doubles as
+ * ag_render_depth reads them; near (1) HOST double.  Background: mode 0 the colour color0; mode 1 bg = (n_bg,H,W,4) uint8 images (4-byte
+ * aligned; the alpha byte is ignored); mode 2 bg = (n_bg,H,W) int32 id images and palette (n_pal) int32 colours: palette[id % n_pal] for
+ * id >= 0, color0 for -1 (the table), color1 otherwise (nothing).  A background index outside 0 .. n_bg - 1 gives color0.
+ * Point i in camera c: d = float64(p) - t, c_r = (R[0,r] d_0 + R[1,r] d_1) + R[2,r] d_2; valid iff c_2 > near; x = trunc(fx (c_0 / c_2) + cx),
+ * y likewise; invalid if either is not finite or exceeds AG_DRAW_MAX_COORD in magnitude.  A primitive is dropped if a point or style index
+ * is out of range (never dereferenced), its kind, size or layer is none of the above, or an endpoint it uses is invalid; a frame's range is
+ * clipped to 0 .. n_prim and is empty for a camera outside 0 .. C - 1.
+ * Coverage of pixel p, int64: disc (p - a)^2 <= size^2; segment with d = b - a, L2 = d.d, q = p - a, s = q.d, X = q_x d_y - q_y d_x:
+ * L2 == 0 or s < 0: 4 |p - a|^2 <= size^2; s > L2: 4 |p - b|^2 <= size^2; otherwise 4 X^2 <= size^2 L2.
+ * Paint: base = background; every covering layer-0 primitive in ascending index sets base; top = base; every covering layer-1 primitive in
+ * ascending index sets top; per channel out = (top alpha + base (256 - alpha) + 128) >> 8, alpha in 0 .. 256; the alpha byte of out is 255.
+ * Out: out (F,H,W,4) uint8.  scratch: ag_draw_scratch_bytes(n_pts, C) bytes, the projected points.
+ * One 256-thread workgroup per (frame, AG_RENDER_TILE x AG_RENDER_TILE pixels), the primitives staged through LDS in chunks of AG_RENDER_CHUNK
+ * and compacted in index order; every pixel written once.
+ * AG_ERR_ARG, nothing launched: a null pts / prims / styles / frames / cams / near / scratch / out, F or C < 1, a negative count, H or W outside
+ * 1 .. AG_RENDER_MAX_SIDE, alpha outside 0 .. 256, a mode outside 0 .. 2, a mode 1 or 2 without images, a mode 2 without a palette, a scratch
+ * that is too small, F x tiles beyond one launch.  No host synchronisation, no atomics, no allocation: safe to capture. */
+#define AG_DRAW_MAX_SIZE 64
+#define AG_DRAW_MAX_COORD 16383
+size_t ag_draw_scratch_bytes(int n_pts, int C);
+int ag_draw(const float *pts, int n_pts, const int32_t *prims, int n_prim, const int32_t *styles, int n_style, const int32_t *frames, int F,
+            const double *cams, int C, const double *near /*host*/, int H, int W, int alpha, int bg_mode, const void *bg, int n_bg,
+            const int32_t *palette, int n_pal, int color0, int color1, void *scratch, size_t scratch_bytes, uint8_t *out, ag_stream_t stream);
 
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
