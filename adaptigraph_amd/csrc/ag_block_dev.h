@@ -50,6 +50,7 @@ __device__ __forceinline__ void four_wave_park(float (&v)[K], float (*red)[4], i
 template <typename T>
 __device__ __forceinline__ T four_wave_total(const T *r) { return (r[0] + r[1]) + (r[2] + r[3]); }
 __device__ __forceinline__ float four_wave_min(const float *r) { return fminf(fminf(r[0], r[1]), fminf(r[2], r[3])); }
+__device__ __forceinline__ float four_wave_max(const float *r) { return fmaxf(fmaxf(r[0], r[1]), fmaxf(r[2], r[3])); }
 
 // ---- rank among the set lanes of a wave-wide flag ----
 // bal = __ballot(flag): how many set lanes lie below `lane`.  With a running count in front it is the slot of an ordered compaction without

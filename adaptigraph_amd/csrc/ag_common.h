@@ -380,6 +380,12 @@ void ag_launch_node_update(const AgWeights &w, const AgFwdArgs &a, const AgPath 
 void ag_launch_edge_encode_ws(const AgWeights &w, const AgFwdArgs &a, const AgPath &p, hipStream_t s);
 void ag_launch_node_update_ws(const AgWeights &w, const AgFwdArgs &a, const AgNodeUpdate &v, hipStream_t s);
 
+// The uniform grid of one sample of the edge builder's cell search (bin_kernel writes it, the selection kernels read it): origin, 1 / cell size,
+// cells per axis (at most kCellMax in all) and the number of binned particles.
+constexpr int kCellMax = 8192;
+struct EdgeGrid { float x0, y0, z0, inv; int nx, ny, nz, total; };
+static_assert(sizeof(EdgeGrid) == 32, "carve_edges: the workspace layout is part of ag_edges_workspace_bytes");
+
 struct AgEdgeArgs {
     const float *pos;            // (B, N, 3) with pos_stride floats between samples
     size_t pos_stride;
@@ -394,10 +400,9 @@ struct AgEdgeArgs {
     int32_t *deg;      // (B*N)
     int32_t *flag;     // (B) connect_tools_all batch_mask
     int32_t *blk_sum;  // scan partials
-    // uniform-grid candidate search (ag_edges.hip: bin_kernel / select_cells_kernel)
-    struct GridParamsPOD { float x0, y0, z0, inv; int nx, ny, nz, total; };
-    void *grid_raw;        // (B) GridParams
-    int32_t *cell_start;   // (B, 8193)
+    // uniform-grid candidate search (ag_edges_select.hip: bin_kernel and the cell kernels)
+    EdgeGrid *grid;        // (B)
+    int32_t *cell_start;   // (B, kCellMax + 1)
     float4 *sorted;        // (B, N) x, y, z, bits(j | tool << 30) in cell order
     // Riders (ag_rollout only; all NULL elsewhere): two pieces of the MODEL step that depend on nothing but what the builder's own launches read or
     // write, carried by those launches instead of a launch of their own (a 15 us latency chain per model step on a nearly idle chip):
@@ -423,11 +428,12 @@ struct AgEdgeArgs {
 };
 enum { AG_RIDER_TAB = 1, AG_RIDER_MAP = 2 };
 int ag_launch_build_edges(const AgEdgeArgs &a, hipStream_t s);      // returns the riders its launches carried (AG_RIDER_*)
+int ag_launch_select_edges(const AgEdgeArgs &a, hipStream_t s);     // its first half (ag_edges_select.hip): sel0 / deg / flag; returns the rider it carried
 
 // Per-node inputs of the edge features (model.py:155-165, 220-253), 64 bytes per node, so that the weight-stationary edge encoder's gather is
 // two indexed 64-byte rows per edge: [attr0, attr1, group0, 0 | v0 | v1 | v2 | x_cur], v_i = state[i+1] - state[i].  The per-edge features are
 // then plain differences of two rows — the same subtractions in the same order as (pr[i+1] - pr[i]) - (ps[i+1] - ps[i]) in edge_features.
-// One thread per node g; shared by edge_node_tab_kernel (ag_edge_encode_ws.hip) and the rider workgroups of bin_kernel (ag_edges.hip).
+// One thread per node g; shared by edge_node_tab_kernel (ag_edge_encode_ws.hip) and the rider workgroups of bin_kernel (ag_edges_select.hip).
 // `class_row0` >= 0 (self-edge elision): rows class_row0 + k, k < AG_SELF_ROWS, are the two endpoints of class k's synthetic self-edge — the class's
 // attribute pair, everything else zero, so that the edge features come out as a real self-loop's: [a, a, |0 - 0|, 0 - 0 ...] (written by thread k).
 __device__ __forceinline__ void ag_edge_node_tab_row(const float *state, const float *attrs, const float *p_instance, int n_inst, int n_p,

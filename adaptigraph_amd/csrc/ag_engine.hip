@@ -61,8 +61,8 @@ void carve_edges(Carver &c, AgEdgeArgs &a)
     a.deg = c.take<int32_t>(rows);
     a.flag = c.take<int32_t>(a.B);
     a.blk_sum = c.take<int32_t>(ag_scan_blocks(rows));
-    a.grid_raw = c.take<int32_t>((size_t)a.B * 8);
-    a.cell_start = c.take<int32_t>((size_t)a.B * 8193);
+    a.grid = c.take<EdgeGrid>((size_t)a.B);
+    a.cell_start = c.take<int32_t>((size_t)a.B * (kCellMax + 1));
     a.sorted = c.take<float4>(rows);
 }
 

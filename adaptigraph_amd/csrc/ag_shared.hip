@@ -15,8 +15,7 @@
 // Every row that is not private has the base's edge list, the base's inputs and only senders whose values equal the base's: its result IS the base
 // row's, and ag_rollout.hip's state update copies it from there.  Summation orders are untouched, so the rollout equals the plain one bit for bit
 // (tests/test_gpu_parity.py: test_shared_state_*).
-#include "ag_block_dev.h"
-#include "ag_common.h"
+#include "ag_edges_dev.h"
 
 namespace {
 
@@ -81,8 +80,8 @@ __global__ __launch_bounds__(256) void shared_stage_kernel(AgSharedArgs a)
 }
 
 // Can this sample differ from the base at all in this step?  Only through a dirty particle, or through a tool that has a particle within the
-// interaction radius — the SAME arithmetic as the edge builder's pair test (separately rounded products, (d - thr) < 0): no pair in radius, no tool
-// edge, whatever top-k does.  One workgroup per sample; base: always.
+// interaction radius — the edge builder's own pair test (pair_dist, in_radius of ag_edges_dev.h): no pair in radius, no tool edge, whatever top-k
+// does.  One workgroup per sample; base: always.
 __global__ __launch_bounds__(256) void shared_active_kernel(AgSharedArgs a)
 {
     constexpr int kTools = 32;
@@ -109,9 +108,8 @@ __global__ __launch_bounds__(256) void shared_active_kernel(AgSharedArgs a)
             if (!mk[i] || tl[i]) continue;
             const float x = pos[i * 3], y = pos[i * 3 + 1], z = pos[i * 3 + 2];
             for (int k = 0; k < nt; ++k) {
-                const float dx = x - tx[k], dy = y - ty[k], dz = z - tz[k];
-                const float d = (dx * dx + dy * dy) + dz * dz;
-                any = any || (d - thr) < 0.0f;
+                const float d = pair_dist(x, y, z, tx[k], ty[k], tz[k]);
+                any = any || in_radius(d, thr);
             }
         }
     const int r = __syncthreads_or(any ? 1 : 0);

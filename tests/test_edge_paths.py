@@ -1,8 +1,8 @@
-"""The edge builder (csrc/ag_edges.hip) on the selection paths that the synth clouds of tests/test_gpu_parity.py never reach, against the oracle
+"""The edge builder (csrc/ag_edges_select.hip, ag_edges.hip) on the selection paths that the synth clouds of tests/test_gpu_parity.py never reach, against the oracle
 (oracle/ag_oracle.c, pinned to the reference by tests/test_oracle_golden.py), exactly: the same edge counts and the same (receiver, sender) lists.
 
 Which kernel serves a call is NOT observed: it is read from `ag_launch_build_edges` and the kernels it launches, and the CPU tests of part 1 tie
-every input of part 2 to the branch it is meant for.  They restate these constants of ag_edges.hip; when one of them changes, the reach tests
+every input of part 2 to the branch it is meant for.  They restate these constants of the builder's sources; when one of them changes, the reach tests
 are what has to follow:
     256                  N >= 256 bins the sample into cells (bin_kernel), below that the brute-force select_kernel scans it
     {5, 10, 20}          the top-k values with a lane-per-receiver kernel; every other top-k at N >= 256 takes select_cells_kernel

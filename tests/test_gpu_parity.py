@@ -138,7 +138,7 @@ def test_edges_connect_tools_all_beyond_the_fast_paths_vs_oracle(material, n_obj
 
 @pytest.mark.parametrize("n_obj,seed", [(300, 1), (2000, 2), (5000, 3)])
 def test_edges_topk20_packed_key_boundary_vs_oracle(n_obj, seed):
-    """Top-k 20 (granular) takes the packed-key selection kernel (csrc/ag_edges.hip select_lanes_packed_kernel): 32-bit keys that
+    """Top-k 20 (granular) takes the packed-key selection kernel (csrc/ag_edges_select.hip select_lanes_packed_kernel): 32-bit keys that
     keep only the leading bits of d.  Clouds built to make the K-th / (K+1)-th candidates (nearly) indistinguishable in those
     bits -- rings of ~45 senders at the same distance up to a few ulps around every centre, exact duplicates (equal d: the tie
     goes to the lower sender index), and a plain dense blob -- must still give the oracle's edge lists bit for bit."""
