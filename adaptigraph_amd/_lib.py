@@ -148,6 +148,10 @@ SIGNATURES = {
     "ag_draw_scratch_bytes": (c_size_t, [c_int] * 2),
     "ag_draw": (c_int, [c_void_p, c_int] * 4 + [c_void_p, c_int, P(c_double)] + [c_int] * 4 + [c_void_p, c_int] * 2 + [c_int] * 2
                 + [c_void_p, c_size_t, c_void_p, c_void_p]),
+    # records as baseline JPEG scans
+    "ag_jpeg_scratch_bytes": (c_size_t, [c_int] * 5),
+    "ag_jpeg_out_bytes": (c_size_t, [c_int] * 5),
+    "ag_jpeg_encode": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
     # training batches assembled on the device
     "ag_gather_clouds": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3),
     "ag_assemble_batch": (c_int, [P(BatchDims)] + [c_void_p] * 8 + [P(BatchOut), c_void_p]),

@@ -9,7 +9,7 @@ import torch
 
 
 def run_closed_loop(env, planner, criteria, n_actions, n_look_ahead, action_lower_lim, action_upper_lim, fps_radius, save_dir=None,
-                    ppm_optimizer=None, use_ppo=False, viz=False, target_state=None, target_box=None):
+                    ppm_optimizer=None, use_ppo=False, viz=False, target_state=None, target_box=None, video=False):
     """plan.py:212-315.  `criteria` maps a cloud (1, n, 3) in simulator units to a 0-d error tensor; action_lower_lim / action_upper_lim are
     (action_dim,) tensors on the planner's device; the random draws are the reference's (`torch.rand` for the first window, then one row per
     step).  With `save_dir` step i writes interaction_{i}.npz with the reference's keys (plan.py:286-295) -- act, act_all, state_pred,
@@ -18,7 +18,9 @@ def run_closed_loop(env, planner, criteria, n_actions, n_look_ahead, action_lowe
     and rgb_vis_{i}_1.png after the second observation (plan.py:262-283): viz.planning_image over the environment's own render, with
     `target_state` (m, 3) in simulator units or `target_box` ((x_min, x_max), (z_min, z_max)) as the overlay.  Drawing needs SimEnv's `render`
     and cameras; it draws no random number and reads nothing the loop does not read, so the actions, the errors and the records are those of
-    viz=False.  -> (res_act_seq (n_actions, action_dim), error_seq of n_actions + 1 floats:
+    viz=False.  With `video` (which needs `viz` and `save_dir`) the same images also go into save_dir/rgb_vis.avi, rgb_vis_{i}_0 then rgb_vis_{i}_1 in
+    step order at 1 fps (plan.py:328-339), Motion-JPEG (jpeg.VideoWriter) encoded where the images are -- on the environment's device, before
+    they are copied for the PNGs -- and nothing else changes.  -> (res_act_seq (n_actions, action_dim), error_seq of n_actions + 1 floats:
     the error before the first action and after every action).
     The window of step i is min(n_actions - i, n_look_ahead) rows, so that act_all and state_pred_all have the length plan.py:284-285 asserts;
     the reference shortens its window one step later and trips those assertions at the last step whenever n_look_ahead > 1 (its shipped
@@ -29,8 +31,11 @@ def run_closed_loop(env, planner, criteria, n_actions, n_look_ahead, action_lowe
     gripper = bool(env.task_config.get("gripper_enable", False))
     if use_ppo and (ppm_optimizer is None or save_dir is None):
         raise ValueError("run_closed_loop: use_ppo needs ppm_optimizer and save_dir (the optimizer reads the recorded interactions)")
+    if video and not (viz and save_dir is not None):
+        raise ValueError("run_closed_loop: video needs viz and save_dir (the video is made of the drawn images)")
     if save_dir is not None:
         os.makedirs(save_dir, exist_ok=True)
+    reel = []      # the video's writer, opened at the first image (which gives the size)
 
     def numpy_of(x):
         return x.detach().cpu().numpy() if isinstance(x, torch.Tensor) else np.asarray(x)
@@ -42,10 +47,15 @@ def run_closed_loop(env, planner, criteria, n_actions, n_look_ahead, action_lowe
         return state.to(device=device, dtype=torch.float32), numpy_of(cloud)
 
     def draw(i, tag, state_init, res, state_after=None):
-        from . import viz
-        viz.write_png(os.path.join(save_dir, f"rgb_vis_{i}_{tag}.png"),
-                      viz.planning_image(env, state_init, res["best_model_output"]["state_seqs"][0][0], numpy_of(res["act_seq"][0]),
-                                         target_state=target_state, target_box=target_box, state_after=state_after))
+        from . import jpeg, viz
+        image = viz.planning_image(env, state_init, res["best_model_output"]["state_seqs"][0][0], numpy_of(res["act_seq"][0]),
+                                   target_state=target_state, target_box=target_box, state_after=state_after)
+        if video:
+            if not reel:
+                reel.append(jpeg.VideoWriter(os.path.join(save_dir, "rgb_vis.avi"), image.shape[0], image.shape[1], 1,
+                                             device=image.device if isinstance(image, torch.Tensor) else None))
+            reel[0].add(image[None])
+        viz.write_png(os.path.join(save_dir, f"rgb_vis_{i}_{tag}.png"), image)
 
     def error_of(cloud):
         return float(criteria(torch.from_numpy(cloud)[None].to(device)).item())
@@ -80,5 +90,7 @@ def run_closed_loop(env, planner, criteria, n_actions, n_look_ahead, action_lowe
         error_seq.append(error_of(pcd_real))
         if use_ppo:
             ppm_optimizer.optimize(i, iterations=50)
+    if reel:
+        reel[0].close()
     planner.n_look_ahead = full_look_ahead
     return res_act_seq, error_seq

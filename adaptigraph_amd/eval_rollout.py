@@ -1,6 +1,6 @@
 """Open-loop evaluation rollouts over a recorded dataset on the engine — SURVEY.md §8f row n3.
 
-Mirrors src/dynamics/rollout/rollout.py (:20-319; its per-step images as numbered PNGs drawn by viz.py, no video) and the graph set-up of
+Mirrors src/dynamics/rollout/rollout.py (:20-319; its per-step images drawn by viz.py, its .jpg files and videos by jpeg.py) and the graph set-up of
 src/dynamics/rollout/graph.py:233-399.  The reference rolls ONE start graph at a time, rebuilding dense Rr/Rs on the host
 and copying state back and forth every step.  Which frames a rollout visits depends only on the frame-pair table, never on
 the predictions, so here the frame schedule of every start graph is resolved on the host up front (`frame_schedule`), the
@@ -133,10 +133,18 @@ def frame_schedule(pairs, n_his, n_frames, current_start, current_end, next_fn, 
 
 
 def _viz_options(config_or_none, dirs):
-    """What rollout_batch's `viz` takes: the directory of every rollout's images, and from rollout_config the optional `viz_size` (H, W) and
-    `viz_radius` (the particles' radius in simulator units; default: the material's simulator default)."""
+    """What rollout_batch's `viz` takes: the directory of every rollout's images, and from rollout_config the optional `viz_size` (H, W),
+    `viz_radius` (the particles' radius in simulator units; default: the material's simulator default), `viz_format` ("png", the default, or
+    "jpg": the reference's own file names) and `viz_video` (pred.avi, gt.avi and both.avi in every directory).  The drivers without a config
+    take the same keys as their `viz` argument: True, or a dict such as {"viz_video": True}."""
+    if isinstance(config_or_none, dict) and "rollout_config" not in config_or_none:
+        config_or_none = {"rollout_config": config_or_none}      # (a driver's `viz` dict)
     rc = (config_or_none or {}).get("rollout_config", {})
-    return {"dirs": list(dirs), "size": tuple(rc.get("viz_size", (720, 1280))), "radius": rc.get("viz_radius")}
+    fmt = rc.get("viz_format", "png")
+    if fmt not in ("png", "jpg"):
+        raise ValueError('rollout_config: viz_format is "png" or "jpg"')
+    return {"dirs": list(dirs), "size": tuple(rc.get("viz_size", (720, 1280))), "radius": rc.get("viz_radius"), "format": fmt,
+            "video": bool(rc.get("viz_video", False))}
 
 
 @torch.no_grad()
@@ -178,7 +186,8 @@ def rollout_batch(model, device, graphs, fps_idx_lists, schedules, eef_pos_list,
         vz.write_rollout_record(viz["dirs"], schedules, torch.stack([x[:, :max_nobj] for x in read_states], 1), torch.from_numpy(gt_start).to(dev),
                                 eef_start, edges, [len(f) for f in fps_idx_lists], max_nobj,
                                 [[np.asarray(obj_pos_list[b][s]) for s, _ in sched] for b, sched in enumerate(schedules)],
-                                dataset_config["materials"][0], dev, radius=viz["radius"], H=viz["size"][0], W=viz["size"][1])
+                                dataset_config["materials"][0], dev, radius=viz["radius"], H=viz["size"][0], W=viz["size"][1],
+                                video=viz.get("video", False), fmt=viz.get("format", "png"))
 
     state, action, attrs, p_instance = stack("state").float(), stack("action").float(), stack("attrs"), stack("p_instance")
     state_mask, eef_mask, obj_mask = stack("state_mask"), stack("eef_mask"), stack("obj_mask")
@@ -223,12 +232,14 @@ def rollout_from_start_graph(graph, fps_idx_list, dataset_config, material_confi
                              current_start, current_end, get_next_pair_or_break_func, pairs, save_dir=None, viz=False,
                              imgs=None, cam_info=None, scripted=False):
     """Reference signature (rollout.py:20-143) for one start graph.  `viz` (with `save_dir`) writes every step's images there, over the sphere
-    splat of the recorded particles: `imgs` and `cam_info` are not read.  `scripted`: see rollout_batch."""
+    splat of the recorded particles: `imgs` and `cam_info` are not read; `viz` may be a dict of rollout_config's viz_* keys, so
+    viz={"viz_video": True} also writes pred.avi, gt.avi and both.avi (_viz_options).  `scripted`: see rollout_batch."""
     n_his = dataset_config["n_his"]
     assert eef_pos.shape[0] == obj_pos.shape[0]
     sched = frame_schedule(pairs, n_his, obj_pos.shape[0], current_start, current_end, get_next_pair_or_break_func)
     return rollout_batch(model, device, [graph], [fps_idx_list], [sched], [eef_pos], [obj_pos], dataset_config,
-                         viz=_viz_options(None, [save_dir]) if viz and save_dir is not None else None, scripted=scripted)[0]
+                         viz=_viz_options(viz if isinstance(viz, dict) else None, [save_dir]) if viz and save_dir is not None else None,
+                         scripted=scripted)[0]
 
 
 def _episode_first_pairs(dataset_config, episode_idx):
@@ -255,11 +266,11 @@ def _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_i
 
 def rollout_episode_pushes(model, device, dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param,
                            save_dir, viz=False, imgs=None, cam_info=None, fps_device=None, scripted=False):
-    """-> [error list per push]; writes error_<i>.txt per push like the reference (rollout.py:145-196; no plots/videos) and, with `viz`, every
-    step's images beside them."""
+    """-> [error list per push]; writes error_<i>.txt per push like the reference (rollout.py:145-196; no plots) and, with `viz`, every
+    step's images beside them; viz={"viz_video": True} (a dict of rollout_config's viz_* keys) writes their videos (rollout.py:197-203) too."""
     starts = _episode_starts(dataset_config, material_config, eef_pos, obj_pos, episode_idx, pairs, physics_param, device,
                              fps_device=fps_device)
-    errs = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config, viz=_viz_options(None, [save_dir] * len(starts)) if viz else None,
+    errs = rollout_batch(model, device, *map(list, zip(*starts)), dataset_config, viz=_viz_options(viz if isinstance(viz, dict) else None, [save_dir] * len(starts)) if viz else None,
                          scripted=scripted) if starts else []
     for i, e in enumerate(errs):
         np.savetxt(os.path.join(save_dir, f"error_{i + 1}.txt"), np.array(e))

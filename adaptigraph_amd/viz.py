@@ -1,8 +1,8 @@
 """Rollout and planning records drawn as images: what the reference draws with cv2 at every stage -- `visualize_graph`
 (src/dynamics/rollout/graph.py:44-230: key points, tool, edges, motion trails, pred | gt side by side) and `visualize_img`
 (src/planning/plan_utils.py:104-300: start state and edges, action arrows, predicted state and target as a half-transparent overlay) -- for the
-project's own records.  What it is NOT: our coverage rule is not cv2's Bresenham lines or its anti-aliasing; there is no text and no video
-container (numbered PNGs only); particles are spheres (the background is render.py's sphere splat); the overlay is a fixed-point blend.
+project's own records.  What it is NOT: our coverage rule is not cv2's Bresenham lines or its anti-aliasing; there is no text (JPEG files and
+videos of the frames: jpeg.py); particles are spheres (the background is render.py's sphere splat); the overlay is a fixed-point blend.
 
 Two paths, one result.  `draw_host` is the statement of the arithmetic, in numpy; `draw(..., device=)` / `DeviceCanvas.launch` is one call of
 csrc/ag_draw.hip (two launches) and returns the same bits.  A frame is drawn from a DISPLAY LIST, primitives in paint order over a background:
@@ -591,10 +591,13 @@ def planning_image(env, state_init, state_pred, action, *, target_state=None, ta
 
 
 def write_rollout_record(dirs, schedules, pred, gt, eef, edges, n_kp, max_nobj, particles, material, device=None, radius=None, H=720, W=1280,
-                         camera=0, batch=None):
+                         camera=0, batch=None, video=False, fmt="png"):
     """Every step of every rollout of a batch as {start:06}_{end:06}_{pred,gt,both}.png in dirs[b] (graph.py:163-225's names with png for jpg;
-    `both` is pred | gt side by side).  schedules[b] = [(start, end)] per step; pred, gt (B, T, max_nobj, 3), eef (B, T, n_eef, 3) and edges as
-    rollout_frames takes them, all at frame `start`; edges[t] a graph.CSREdges of the whole batch at step t; particles[b][t] (n, 3): the
+    `both` is pred | gt side by side).  fmt="jpg": the reference's own names, baseline JPEG files (jpeg.py) -- on the device encoded from the
+    drawn frames where they are (`both` from the device-side concatenation), so that only the compressed bytes are copied to the host.
+    `video`: every directory drawn into also gets pred.avi, gt.avi and both.avi, Motion-JPEG at 10 fps of its frames in file-name order
+    (rollout.py:197-203); the encoded frames are kept in host memory until the last chunk is drawn.
+    schedules[b] = [(start, end)] per step; pred, gt (B, T, max_nobj, 3), eef (B, T, n_eef, 3) and edges as rollout_frames takes them, all at frame `start`; edges[t] a graph.CSREdges of the whole batch at step t; particles[b][t] (n, 3): the
     recorded particles of frame `start`, the background (a sphere splat from camera `camera` of render.default_cameras, the reference's
     cam = 0, where the reference shows the recorded camera image).  Everything is in simulator units and goes to the board frame with the
     task's sim_real_ratio; `radius` is the particles' (default: the material's simulator default `r`; the pile's is per scene, 0.1 here).
@@ -603,7 +606,10 @@ def write_rollout_record(dirs, schedules, pred, gt, eef, edges, n_kp, max_nobj, 
     device=None: the host statements.  -> the paths written."""
     import os
 
-    from . import configs, sim_env
+    from . import configs, jpeg, sim_env
+    if fmt not in ("png", "jpg"):
+        raise ValueError('write_rollout_record: fmt is "png" or "jpg"')
+    coded, reels = video or fmt == "jpg", {}
     ratio = float(configs.task_config(material)["sim_real_ratio"])
     if radius is None:
         radius = getattr(sim_env.SIMULATORS[material][0], "r", 0.1)
@@ -627,6 +633,9 @@ def write_rollout_record(dirs, schedules, pred, gt, eef, edges, n_kp, max_nobj, 
         renderer = render.DeviceRenderer(*cam, H, W, (0.0, 0.0, 1.0, 0.0), E=per, device=device)
         canvas = DeviceCanvas(cams, H, W, 2 * per, max(hi - lo for lo, hi in spans), device=device)
         palette, rr_dev = torch.tensor(PALETTE, dtype=torch.int32, device=device), torch.from_numpy(rr).to(device)
+        if coded:
+            encoders = (jpeg.DeviceEncoder(H, W, min(2 * per, jpeg.frames_per_launch(H, W)), device=device),
+                        jpeg.DeviceEncoder(H, 2 * W, min(per, jpeg.frames_per_launch(H, 2 * W)), device=device))
     written = []
     for k, chunk in enumerate(chunks):
         j0, (lo, hi) = k * per, spans[k]
@@ -642,16 +651,35 @@ def write_rollout_record(dirs, schedules, pred, gt, eef, edges, n_kp, max_nobj, 
         if device is None:
             ids = render.render_depth_host(scene, n, rr, *cam, H, W, (0.0, 0.0, 1.0, 0.0))[1][:, 0]
             images = draw_host(pts[lo:hi], prims[p0:p1] - shift, styles, fr, cams, H, W, 128, 2, ids, PALETTE, TABLE_COLOR, VOID_COLOR)
+            if coded:
+                both = np.concatenate([images[0::2], images[1::2]], 2)
+                files = jpeg.encode_jpeg(images), jpeg.encode_jpeg(both)
         else:
             ids = renderer.launch(torch.from_numpy(scene).to(device), torch.from_numpy(n).to(device), rr_dev)[1][:, 0]
             images = canvas.launch(pts[lo:hi].contiguous(), (prims[p0:p1] - torch.from_numpy(shift).to(device)).contiguous(), styles,
-                                   torch.from_numpy(fr).to(device), 128, 2, ids.contiguous(), palette, TABLE_COLOR, VOID_COLOR).cpu().numpy()
+                                   torch.from_numpy(fr).to(device), 128, 2, ids.contiguous(), palette, TABLE_COLOR, VOID_COLOR)
+            if coded:      # where the frames are: pred and gt as drawn, `both` their concatenation on the device
+                files = encoders[0].encode(images), encoders[1].encode(torch.cat([images[0::2], images[1::2]], 2).contiguous())
+            if fmt == "png":
+                images = images.cpu().numpy()
         for e, (b, t) in enumerate(chunk):
             start, end = schedules[b][t]
             stem = os.path.join(dirs[b], f"{int(start):06}_{int(end):06}")
-            for name, image in (("pred", images[2 * e]), ("gt", images[2 * e + 1]), ("both", np.concatenate([images[2 * e], images[2 * e + 1]], 1))):
-                write_png(f"{stem}_{name}.png", image)
-                written.append(f"{stem}_{name}.png")
+            for name in ("pred", "gt", "both"):
+                data = None if not coded else files[1][e] if name == "both" else files[0][2 * e + (name == "gt")]
+                if fmt == "png":
+                    write_png(f"{stem}_{name}.png", np.concatenate([images[2 * e], images[2 * e + 1]], 1) if name == "both" else
+                              images[2 * e + (name == "gt")])
+                else:
+                    with open(f"{stem}_{name}.jpg", "wb") as fh:
+                        fh.write(data)
+                written.append(f"{stem}_{name}.{fmt}")
+                if video:
+                    reels.setdefault((dirs[b], name), []).append((os.path.basename(stem), data))
+    for (d, name), frames in reels.items():      # a directory's frames in file-name order, whichever rollouts they came from
+        with jpeg.VideoWriter(os.path.join(d, f"{name}.avi"), H, 2 * W if name == "both" else W, 10) as out:
+            out.add([data for _, data in sorted(frames, key=lambda x: x[0])])
+        written.append(os.path.join(d, f"{name}.avi"))
     return written
 
 
@@ -660,7 +688,7 @@ def _host(a):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
-# PNG files: 8-bit RGB, filter 0, from the standard library alone.  There is no video container: numbered PNGs only.
+# PNG files: 8-bit RGB, filter 0, from the standard library alone.  (JPEG files and Motion-JPEG videos: jpeg.py.)
 # ---------------------------------------------------------------------------------------------------------------------
 _PNG_MAGIC = b"\x89PNG\r\n\x1a\n"
 

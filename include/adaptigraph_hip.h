@@ -668,6 +668,38 @@ int ag_draw(const float *pts, int n_pts, const int32_t *prims, int n_prim, const
             const double *cams, int C, const double *near /*host*/, int H, int W, int alpha, int bg_mode, const void *bg, int n_bg,
             const int32_t *palette, int n_pal, int color0, int color1, void *scratch, size_t scratch_bytes, uint8_t *out, ag_stream_t stream);
 
+/* ---- records as baseline JPEG scans (what the reference writes with cv2 and merges into videos: src/dynamics/rollout/graph.py:163-225,
+ * rollout.py:194-203, src/planning/plan.py:328-339): the entropy-coded scans of F frames of H x W pixels in FIVE launches.  The
+ * arithmetic is stated by adaptigraph_amd/jpeg.py:jpeg_scan_host, all integers, and repeated here operation for operation, so the call gives the
+ * statement's bytes; the headers (SOI .. SOS), EOI and the AVI container of a Motion-JPEG video are host code there.  Not: mp4, inter-frame
+ * coding, optimised or progressive Huffman tables.
+ * DEVICE arrays: images (F,H,W,channels) uint8, channels 4 as ag_draw writes them (R, G, B, alpha; 4-byte aligned; alpha is ignored) or 3.
+ * Colour: JFIF YCbCr in 16-bit fixed point, clamped to 0 .. 255.  subsampling AG_JPEG_444: an MCU is 8 x 8 pixels = the blocks Y, Cb, Cr;
+ * AG_JPEG_420: 16 x 16 = Y00, Y01, Y10, Y11, Cb, Cr with chroma (a + b + c + d + 2) >> 2; the image is extended to whole MCUs by repeating its
+ * last column and row.  Integer 8 x 8 DCT of sample - 128 in two matrix passes (13-bit coefficients; every intermediate inside int32), the Annex K
+ * quantisation tables scaled by quality 1 .. 100 with the IJG rule, division to nearest and symmetric in sign, the four Annex K Huffman tables,
+ * one restart interval every `restart` MCUs: the DC predictors reset, the segment is padded with 1-bits to a byte, every 0xFF byte is followed
+ * by 0x00, RSTm (m mod 8) stands between segments and not after the last.
+ * Out: out = the frames' scans back to back, offsets (F + 1) int64: frame f is out[offsets[f] .. offsets[f + 1]).
+ * A segment is at most 2 * AG_JPEG_BLOCK_BYTES * blocks-per-MCU (3 or 6) * restart + 2 bytes = its SLOT (a block's bits, 11 + 11 of DC and
+ * 63 * (16 + 10) of AC, are under AG_JPEG_BLOCK_BYTES bytes; stuffing at most doubles them; 2 for the marker).  With M = MCUs per frame,
+ * S = ceil(M / restart) segments per frame and G = F S:  ag_jpeg_out_bytes = G * slot;  ag_jpeg_scratch_bytes = the sum, each part rounded up
+ * to 256 bytes, of the coefficients (F M blocks-per-MCU * 64 int16), a slot per segment (G * slot), two int32 per segment (4 G + 4 G) and the
+ * scan's sums (4 (G / 256 + 2)).  Both queries return 0 for arguments the call refuses.
+ * One workgroup codes one segment, its unstuffed bits in LDS: AG_JPEG_MAX_RESTART * 6 * AG_JPEG_BLOCK_BYTES = 19 968 bytes.
+ * AG_ERR_ARG, nothing launched: a null images / scratch / out / offsets, F < 1, H or W outside 1 .. AG_RENDER_MAX_SIDE, channels not 3 or 4,
+ * quality outside 1 .. 100, an unknown subsampling, restart outside 1 .. AG_JPEG_MAX_RESTART, unaligned RGBA images, a scratch or an out that is
+ * smaller than its query, a worst case beyond 2^31 - 1 bytes (hand in fewer frames).  No host synchronisation, no allocation, no memset, every
+ * scratch word written before it is read, integer atomics in LDS only (exact in any order): the same bytes on every call, safe to capture. */
+#define AG_JPEG_444 0
+#define AG_JPEG_420 1
+#define AG_JPEG_MAX_RESTART 16
+#define AG_JPEG_BLOCK_BYTES 208
+size_t ag_jpeg_scratch_bytes(int F, int H, int W, int subsampling, int restart);
+size_t ag_jpeg_out_bytes(int F, int H, int W, int subsampling, int restart);
+int ag_jpeg_encode(const uint8_t *images, int F, int H, int W, int channels, int quality, int subsampling, int restart, void *scratch,
+                   size_t scratch_bytes, uint8_t *out, size_t out_bytes, int64_t *offsets, ag_stream_t stream);
+
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
  *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
