@@ -152,6 +152,16 @@ SIGNATURES = {
     "ag_jpeg_scratch_bytes": (c_size_t, [c_int] * 5),
     "ag_jpeg_out_bytes": (c_size_t, [c_int] * 5),
     "ag_jpeg_encode": (c_int, [c_void_p] + [c_int] * 7 + [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p]),
+    # object masks from colour images
+    "ag_segment_tile_sizes": (None, [P(c_int), P(c_int)]),
+    "ag_segment_scratch_bytes": (c_size_t, [c_int] * 3),
+    "ag_segment_color_mask": (c_int, [c_void_p] + [c_int] * 4 + [P(c_int32), c_int, c_void_p, c_void_p]),
+    "ag_segment_morph": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ag_segment_label": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_size_t] + [c_void_p] * 3),
+    "ag_segment_components": (c_int, [c_void_p] * 2 + [c_int] * 4 + [c_void_p] * 2),
+    "ag_segment_select": (c_int, [c_void_p] + [c_int] * 6 + [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ag_segment_fill_holes": (c_int, [c_void_p] + [c_int] * 4 + [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "ag_segment_keep": (c_int, [c_void_p] * 2 + [c_int] * 3 + [c_void_p] * 2),
     # training batches assembled on the device
     "ag_gather_clouds": (c_int, [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 2 + [c_void_p] * 3),
     "ag_assemble_batch": (c_int, [P(BatchDims)] + [c_void_p] * 8 + [P(BatchOut), c_void_p]),

@@ -1,6 +1,8 @@
 """The geometry between the cameras and `state_cur`: depth images -> tabletop cloud -> key points (src/planning/perception.py:151-256
 `get_tabletop_points`, :318-349 `get_state_cur`), without the vision models: GroundingDINO and SAM only contribute a boolean keep-mask per
-camera, and that mask is an input here.  Colours are not carried (the reference uses them for drawing only).
+camera, and that mask is an input here.  What the reference does with the models' masks (:176-209, ~(mask_table & ~mask_obj)) is
+`segment.keep_mask`, which makes the mask from a colour image by colour keys, morphology and connected components instead of a learned model;
+`SimEnv(masks="color")` feeds it to this module.  Colours are not carried into the cloud (the reference uses them for drawing only).
 
 The reference does this stage with numpy and open3d (`crop`, `voxel_down_sample`, `remove_statistical_outlier`).  open3d is not vendored and
 was not available when this was written, so, as `sampling.py` does for DGL's sampler, the algorithm is RESTATED below as host code in numpy

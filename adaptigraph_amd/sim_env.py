@@ -53,12 +53,20 @@ class SimEnv:
     RopeScene / PileScene / ClothScene / BoxScene with E = 1 (copied; `env.scene` is the current one, host arrays, or device tensors in x, v on the device
     path); `task_config` gives sim_real_ratio and push_length; `cameras` = (R_list, t_list, intr_list) in the board frame (default:
     render.default_cameras); `params` the simulator's parameters (default: the material's).  Keyword-only: `image_size` (H, W) of the cameras,
-    `stride` of the perception, `bbox` (3, 2) the board-frame crop box, `near`, `far` the depth range in metres."""
+    `stride` of the perception, `bbox` (3, 2) the board-frame crop box, `near`, `far` the depth range in metres; `masks` where the keep-mask of
+    an observation comes from: "ids" (the default) the renderer's id image, privileged knowledge; "color" the environment's own colour images
+    through segment.keep_mask with `table_keys` (default: ColorKey.exact(viz.TABLE_COLOR)), what a user with real cameras would do."""
 
     def __init__(self, material, scene, task_config, cameras=None, device="cuda:0", params=None, *, image_size=(720, 1280), stride=4, bbox=None,
-                 near=0.05, far=4.0):
+                 near=0.05, far=4.0, masks="ids", table_keys=None):
         if material not in MATERIALS:
             raise ValueError(f"SimEnv: material must be one of {MATERIALS}; got {material!r}")
+        if masks not in ("ids", "color"):
+            raise ValueError(f"SimEnv: masks must be \"ids\" or \"color\"; got {masks!r}")
+        self.masks, self.table_keys = masks, table_keys
+        if masks == "color" and table_keys is None:
+            from . import segment, viz
+            self.table_keys = [segment.ColorKey.exact(viz.TABLE_COLOR)]
         if scene.E != 1:
             raise ValueError("SimEnv: one episode per environment (E = 1)")
         self.material, self.task_config = material, task_config
@@ -121,21 +129,38 @@ class SimEnv:
                                    viz.TABLE_COLOR, viz.VOID_COLOR)
 
     def get_obs(self, get_color=False, get_depth=True):
-        """{"depth_i": (1, H, W) float32 in metres, "mask_i": (1, H, W) bool = the pixel shows a particle} per camera i (real_env.py:152-198 with
-        one observation step) and, with `get_color`, "color_i": (1, H, W, 3) uint8, the sphere splat in `color`'s colours.  The mask is what the
-        reference gets from its detection and segmentation models."""
+        """{"depth_i": (1, H, W) float32 in metres, "mask_i": (1, H, W) bool} per camera i (real_env.py:152-198 with one observation step) and,
+        with `get_color`, "color_i": (1, H, W, 3) uint8, the sphere splat in `color`'s colours.  The mask stands for what the reference gets
+        from its detection and segmentation models.  masks="ids": the pixel shows a particle, read off the renderer's id image.  masks="color":
+        the environment looks at its own colour images -- rendered whatever `get_color` says, by the one ag_draw call of `color` -- and the mask
+        is segment.keep_mask(color, table_keys): every pixel that is not table (perception.py:203-209).  The images are flat-coloured, so that
+        is ids != render.ID_PLANE; it differs from the "ids" mask on the void pixels only, whose depth 0 depth_to_points drops under
+        depth_threshold = (0, far), so `get_state_cur` is the same, bit for bit."""
         obs = {}
+        by_color = self.masks == "color" and get_depth
         if get_depth or get_color:
             depth, ids = self.render()
-        if get_color:
+        if get_color or by_color:
             rgba = self.color(ids)
+        if get_color:
             for i in range(len(self.R_list)):
                 obs[f"color_{i}"] = rgba[i][None, :, :, :3]
         if get_depth:
+            keep = self._keep_mask(rgba) if by_color else ids >= 0
             for i in range(len(self.R_list)):
                 obs[f"depth_{i}"] = depth[i][None]
-                obs[f"mask_{i}"] = (ids[i] >= 0)[None]
+                obs[f"mask_{i}"] = keep[i][None]
         return obs
+
+    def _keep_mask(self, rgba):
+        """segment.keep_mask of the colour images (C, H, W, 4) -> (C, H, W) bool, on the environment's path; a tensor of its own on the device
+        (a copy out of the segmenter's buffer), so an observation keeps its masks as it does with masks="ids"."""
+        from . import segment
+        if self.device is None:
+            return segment.keep_mask_host(rgba, self.table_keys)
+        if getattr(self, "_segmenter", None) is None:
+            self._segmenter = segment.DeviceSegmenter(len(self.R_list), self.H, self.W, self.device)
+        return self._segmenter.keep_mask(rgba, self.table_keys).clone()
 
     def get_intrinsics(self):
         return [np.array(K, np.float64) for K in self.intr_list]

@@ -700,6 +700,67 @@ size_t ag_jpeg_out_bytes(int F, int H, int W, int subsampling, int restart);
 int ag_jpeg_encode(const uint8_t *images, int F, int H, int W, int channels, int quality, int subsampling, int restart, void *scratch,
                    size_t scratch_bytes, uint8_t *out, size_t out_bytes, int64_t *offsets, ag_stream_t stream);
 
+/* ---- object masks from colour images (what the reference does with the masks of its detection and segmentation models,
+ * src/planning/perception.py:176-209: join the "table" / "sheet" masks and the object masks, mask_table & ~mask_obj, keep every pixel that is NOT
+ * table), with classical stages in the models' place: colour keys, square morphology, connected components, selection by area, hole filling
+ * (DESIGN.md 8.18).  The arithmetic is stated by adaptigraph_amd/segment.py in numpy integers and repeated here operation for operation: every
+ * result equals the statement's bit for bit.  Not: a learned model, text prompts, instances mapped to p_instance, watershed / grab-cut.
+ * DEVICE arrays: images (C,H,W,channels) uint8, channels 4 (R, G, B, alpha; 4-byte aligned; alpha is ignored) or 3; masks (C,H,W) uint8, non-zero =
+ * set, written as 0 / 1; labels (C,H,W) int32; count (C) int32.  Every image of a call is treated alone.
+ * Shapes: 1 <= C <= 65535, H, W >= 1, H W <= 2^31 - 257 (a pixel's index is an int32), H <= 65535 AG_SEGMENT_TILE_H.  ag_segment_scratch_bytes
+ * = the sum, each part rounded up to 256 bytes, of three int32 images (12 C H W), the scan's sums (4 C (H W / 256 + 2)), the selection's candidates
+ * (64 C ceil(H W / 256) + 8 C) and two masks (2 C H W); 0 for a shape the calls refuse.  The calls that take scratch share it: calls on one stream
+ * may use the same buffer.
+ * ag_segment_color_mask (the models' part): integer HSV of a pixel, with mx, mn the channel maximum and minimum and d = mx - mn: V = mx;
+ *   S = 0 if mx = 0, else (255 d + mx / 2) / mx; H = 0 if d = 0, else by the maximum channel, r before g before b: floor((60 (g - b) + d / 2) / d)
+ *   mod 360, floor((60 (b - r) + d / 2) / d) + 120 mod 360, floor((60 (r - g) + d / 2) / d) + 240 mod 360 (floor toward minus infinity).  keys:
+ *   HOST, n_keys <= AG_SEGMENT_MAX_KEYS rows of h_lo, h_hi, s_lo, s_hi, v_lo, v_hi, inclusive; h_lo > h_hi wraps through 359 -> 0; they travel as
+ *   kernel arguments.  mask = a pixel lies in any key's box.  One launch.
+ * ag_segment_morph: op AG_SEGMENT_ERODE / _DILATE / _OPEN / _CLOSE with the (2 radius + 1) square, 0 <= radius <= AG_SEGMENT_MAX_RADIUS; pixels
+ *   outside the image are background for every operation.  A row pass and a column pass per erosion or dilation: two or four launches.  out
+ *   may be mask.
+ * ag_segment_label: the connected components of the set pixels under connectivity 4 or 8 (perception.py:176-190 receives them as instance masks).
+ *   labels: 0 for background, else 1 .. count[c] in ascending order of a component's lowest row-major pixel index, restarting in every image;
+ *   complete for any number of components.  Five launches: tile-local union-find in LDS over row runs, unions across the tile borders in global
+ *   memory (agent-scope atomics only), flatten, the two-pass scan over the roots, relabel.  A root is its component's lowest index, whatever
+ *   the order of the unions.
+ * ag_segment_components: table (C,max_labels,8) int64 rows area, x_min, y_min, x_max, y_max, sum_x, sum_y, touches_border of labels
+ *   1 .. min(count[c], max_labels); the other rows zero.  Integer atomics, one set per row run.  Two launches.
+ * ag_segment_select: out = the components of mask with at least min_area pixels and, with keep_largest = k in 1 .. AG_SEGMENT_MAX_KEEP, of
+ *   those the k largest, equal areas by the lower label (perception.py:191-202 picks masks by label; here by size); keep_largest 0 keeps all.
+ *   Areas live at the root pixels: any number of components.  Five launches, seven with keep_largest.  out may be mask (the last launch writes it).
+ * ag_segment_fill_holes: out = mask and every background component that no pixel of the image border belongs to, the background under the dual
+ *   connectivity (4 where the foreground's is 8).  Five launches.  out may be mask.
+ * ag_segment_keep: out = ~(table & ~objects), perception.py:203-209; objects may be NULL (no object mask: out = ~table).  One launch.
+ * AG_ERR_ARG, nothing launched: a null pointer, a shape outside the ranges above, channels not 3 or 4, more than AG_SEGMENT_MAX_KEYS keys,
+ * unaligned RGBA images, an unknown op, a radius, connectivity or keep_largest out of range, max_labels < 1; AG_ERR_WS: a scratch smaller than
+ * ag_segment_scratch_bytes.  No host synchronisation, no allocation, no memset (every per-call word is written by a kernel of the call before it
+ * is read), launch counts that depend on the arguments and never on the images, integer arithmetic only: the same bits on every call, safe to
+ * capture. */
+#define AG_SEGMENT_TILE_H 16
+#define AG_SEGMENT_TILE_W 64
+#define AG_SEGMENT_MAX_KEYS 8
+#define AG_SEGMENT_MAX_KEEP 8
+#define AG_SEGMENT_MAX_RADIUS 8
+#define AG_SEGMENT_ERODE 0
+#define AG_SEGMENT_DILATE 1
+#define AG_SEGMENT_OPEN 2
+#define AG_SEGMENT_CLOSE 3
+void ag_segment_tile_sizes(int *tile_h, int *tile_w);
+size_t ag_segment_scratch_bytes(int C, int H, int W);
+int ag_segment_color_mask(const uint8_t *images, int C, int H, int W, int channels, const int32_t *keys /*host*/, int n_keys, uint8_t *mask,
+                          ag_stream_t stream);
+int ag_segment_morph(const uint8_t *mask, int C, int H, int W, int op, int radius, void *scratch, size_t scratch_bytes, uint8_t *out,
+                     ag_stream_t stream);
+int ag_segment_label(const uint8_t *mask, int C, int H, int W, int connectivity, void *scratch, size_t scratch_bytes, int32_t *labels,
+                     int32_t *count, ag_stream_t stream);
+int ag_segment_components(const int32_t *labels, const int32_t *count, int C, int H, int W, int max_labels, int64_t *table, ag_stream_t stream);
+int ag_segment_select(const uint8_t *mask, int C, int H, int W, int connectivity, int min_area, int keep_largest, void *scratch,
+                      size_t scratch_bytes, uint8_t *out, ag_stream_t stream);
+int ag_segment_fill_holes(const uint8_t *mask, int C, int H, int W, int connectivity, void *scratch, size_t scratch_bytes, uint8_t *out,
+                          ag_stream_t stream);
+int ag_segment_keep(const uint8_t *table, const uint8_t *objects, int C, int H, int W, uint8_t *out, ag_stream_t stream);
+
 /* ---- training batches assembled on the device (SURVEY.md §8f row n4 data side): DynDataset.__getitem__ for B samples at once plus their
  * collation, src/dynamics/dataset/dataset.py:10-252, with the dataset resident in HBM:
  *   obj_store   fp32: every episode's object positions (T_e, N_e, 3), one after the other
